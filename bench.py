@@ -11,7 +11,12 @@ configs[3] / [4] as extra keys (`prithvi_mae`, `prithvi_seg_frozen`, `prithvi_se
 headline `value` is always configs[1].  N > 1 adds `allreduce` (what the gradient all-reduce costs) and
 `prithvi_mae` = the data-parallel Prithvi-100M MAE step (configs[4]) on the same ranks, under a watchdog.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+`--steps K` timed steps follow `--warmup W` untimed ones; `ms_per_step` in the line is the time of one timed step.  Inputs and
+initial weights are seeded, so the same arguments give the same inputs on every run.  `--dump-outputs DIR` writes what the last
+timed step computed (loss, logits, gradients, updated parameters; see dump_outputs) as float32 .npy files for comparing two builds;
+that step then starts from the seeded starting state, so that its outputs repeat from run to run up to rounding.
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment), or called plainly as `python bench.py --gpus N ...`: the parent process then
@@ -438,6 +443,35 @@ def time_steps(step, n: int, dist, dev) -> float:
     return dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(out_dir, arrays: dict, caps: dict | None = None) -> dict:
+    """Write each array of `arrays` (name -> tensor / ndarray) as out_dir/<name>.npy in float32.  An array with more elements than
+    its cap in `caps` (name -> elements) is written as <name>_sample.npy instead: the elements at `cap` flat indices drawn with
+    DUMP_SAMPLE_SEED and sorted, the same indices for the same array size, so that two runs with the same arguments compare
+    element for element.  Returns {file name: shape}; refuses to write more than DUMP_LIMIT_BYTES in all."""
+    caps = caps or {}
+    files = {}
+    for name, a in arrays.items():
+        t = torch.as_tensor(a).detach()
+        cap = caps.get(name)
+        if cap is not None and t.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, t.numel(), size=cap, dtype=np.int64))
+            files[name + "_sample"] = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+        else:
+            files[name] = t.float().cpu().numpy()
+    total = sum(arr.nbytes for arr in files.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, arr in files.items():
+        np.save(d / f"{name}.npy", arr)
+    return {f"{name}.npy": list(arr.shape) for name, arr in files.items()}
+
+
 def allreduce_report(model, ddp, dist, dev, world: int, step_ms: float, noop_ms: float, calls: list) -> dict:
     """What the gradient all-reduce costs (SURVEY.md §8d evidence for configs[2]): bucket count and bytes per step, the time
     it adds to the step (`ms_exposed` = step with the reducer - the same segmented step with the hook replaced by a no-op,
@@ -647,6 +681,9 @@ def main() -> None:
     ap.add_argument("--bucket-mb", type=float, default=None, help="gradient bucket size of the data-parallel reducer (default: ddp.DEFAULT_BUCKET_MB = 32)")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16-mixed"],
                     help="arithmetic of the HEADLINE run (default f32, the parity path; bf16-mixed is otherwise reported as the extra key `bf16_mixed`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, rank 0): loss, logits, "
+                         "the flat gradient buffer and the flat parameters after the Adam step (seeded samples of the larger ones)")
     args = ap.parse_args()
     global BUCKET_MB
     BUCKET_MB = args.bucket_mb
@@ -710,18 +747,47 @@ def main() -> None:
         if ddp is not None:
             ddp.finish()
         opt.step()
-        return loss
+        return loss, logits
 
     last = {}
 
     def timed_step():
-        last["loss"] = step()
+        last.clear()        # the previous step's logits are freed before this step allocates, as without the dump
+        last["loss"], last["logits"] = step()
+
+    start = None
+    if args.dump_outputs:
+        # The weight-gradient sums use float atomics, so every step's gradients differ from run to run by rounding, and Adam turns
+        # that into a different trajectory (after 25 steps the logits of two runs differ by ~3e-3 of their largest value).  With
+        # --dump-outputs the LAST timed step therefore starts again from the run's seeded starting state (weights, BatchNorm
+        # buffers, Adam moments, drop-connect generator): its outputs then differ between runs by rounding only.
+        start = ({k: v.detach().clone() for k, v in model.state_dict().items()}, torch.cuda.get_rng_state(dev))
+
+    def restart():
+        model.load_state_dict(start[0])
+        opt.step_count, opt._updates = 0, {}
+        if opt.m is not None:
+            opt.m.zero_()
+            opt.v.zero_()
+        torch.cuda.set_rng_state(start[1], dev)
 
     for _ in range(args.warmup):
         step()
-    dt = time_steps(timed_step, args.steps, dist, dev)       # EXACTLY args.steps steps, barrier + synchronize on both sides, MAX over ranks
+    if start is None:
+        dt = time_steps(timed_step, args.steps, dist, dev)   # EXACTLY args.steps steps, barrier + synchronize on both sides, MAX over ranks
+    else:
+        dt = time_steps(timed_step, args.steps - 1, dist, dev)
+        restart()                                             # outside the timed region
+        dt += time_steps(timed_step, 1, dist, dev)
     loss = last["loss"]
     step_ms = dt / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any later leg moves the weights: the last timed step's loss and logits, its gradients, the parameters it left
+        # (that step started from the seeded starting state, see `start`)
+        dumped = dump_outputs(args.dump_outputs, {"loss": loss, "logits": last["logits"], "grads": model._grad_buffer(),
+                                                  "params": model._flat_params},
+                              caps={"logits": 1 << 23, "grads": 1 << 21, "params": 1 << 21})
 
     # ---- outside the timed region: what the all-reduce costs, and N = 1 on the SAME plan ---------------------------------
     allreduce, same_plan = None, None
@@ -839,6 +905,8 @@ def main() -> None:
             "n1_same_plan_tiles_per_s": same_plan,
             "allreduce": allreduce, **extra,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": str(args.dump_outputs), "files": dumped}
     if dist is not None and not args.no_prithvi:
         # N > 1: the data-parallel Prithvi leg (configs[4]).  It is collective, so it runs on every rank after rank 0's profile legs;
         # an extra key must never cost the headline line: a watchdog prints the line without the key and ends the rank if the leg hangs

@@ -120,3 +120,28 @@ def test_launcher_deadline(tmp_path, capfd, monkeypatch):
     monkeypatch.setenv("S2K_LAUNCH_DEADLINE_S", "2")
     assert bench.launch_ranks(2, [], script=str(script)) == 124
     assert "launch deadline" in capfd.readouterr().err
+
+
+def test_dump_outputs_writes_float32_files_and_the_same_seeded_sample_every_time(tmp_path):
+    """`--dump-outputs DIR`: one float32 .npy per output; an output over its cap becomes <name>_sample.npy, the same elements on
+    every run, so that two builds can be compared output for output; the whole dump stays under the 64 MB limit."""
+    import numpy as np
+    import torch
+
+    big = torch.arange(100_000, dtype=torch.float64)
+    arrays = {"loss": torch.tensor(1.5), "logits": torch.randn(2, 4, 8, 8), "params": big}
+    files = bench.dump_outputs(tmp_path / "a", arrays, caps={"params": 1000})
+    assert files == {"loss.npy": [], "logits.npy": [2, 4, 8, 8], "params_sample.npy": [1000]}
+    for name in files:
+        assert np.load(tmp_path / "a" / name).dtype == np.float32
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "logits.npy"), arrays["logits"].numpy())
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 1.5
+    bench.dump_outputs(tmp_path / "b", arrays, caps={"params": 1000})
+    s_a, s_b = np.load(tmp_path / "a" / "params_sample.npy"), np.load(tmp_path / "b" / "params_sample.npy")
+    np.testing.assert_array_equal(s_a, s_b)
+    assert np.all(np.diff(s_a) >= 0) and s_a.max() < 100_000          # sorted indices into the array, values from it
+    import pytest
+
+    with pytest.raises(ValueError, match="limit"):
+        bench.dump_outputs(tmp_path / "c", {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "c").exists()
