@@ -72,10 +72,12 @@ class Case:
         fields["BF16_BASE"] = dst16.off - dst.off // 2
         return ("WEIGHT_PACK", fields), dst, MP, dst16
 
-    def run(self, kind, outputs, tol=1e-4, sum0=(), pre=(), want_variant=None, **fields):
+    def run(self, kind, outputs, tol=1e-4, sum0=(), pre=(), want_variant=None, per_column=(), **fields):
         """sum0: outputs compared after summing their leading (statistics-replica) dimension.
         pre: stage records to run first (e.g. WEIGHT_PACK).  want_variant: the kernel family the stage must have taken
-        (s2k_program_profile_variants: 0 generic, 1 producer / consumer, 2 bf16 MFMA)."""
+        (s2k_program_profile_variants, include/s2k.h: 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads).
+        per_column: outputs whose every last-dim column must also meet `tol` against that column's own max |ref| (a wrong
+        column among larger ones - e.g. a ragged last channel tile - hides under the whole tensor's max)."""
         from s2lc_amd import _lib
 
         prog = Program()
@@ -105,6 +107,18 @@ class Case:
             denom = max(b.abs().max().item(), 1e-20)
             err = (a - b).abs().max().item() / denom
             assert err < tol, f"{kind}:{name}: rel err {err:.3e} (max |ref| {denom:.3e})"
+            if name in per_column:
+                n = ref.shape[-1]
+                a, b = a.reshape(-1, n), b.reshape(-1, n)
+                cerr = (a - b).abs().amax(0) / b.abs().amax(0).clamp_min(1e-20)
+                col = int(cerr.argmax())
+                assert cerr[col] < tol, f"{kind}:{name}: column {col} of {n}: rel err {cerr[col]:.3e} (its max |ref| {b[:, col].abs().max():.3e})"
+
+
+def _shape_ids(table, n):
+    """test ids from the first n columns of each case (the shape), so that a case keeps its id whichever kernel family - a later
+    column - it is pinned to"""
+    return ["-".join(str(v) for v in case[:n]) for case in table]
 
 
 def test_mfma_lane_maps_exact():
@@ -189,11 +203,11 @@ def _conv_case(B, C1, C2, H, W, M, k, s, pt, pl, Ho, Wo, pro1, pro2, gate, bias,
 
 @pytest.mark.parametrize("B,C1,H,W,M,bias,beta,want", [
     (64, 768, 1, 52, 3072, False, 0, 1),       # fc2's data gradient of the MAE encoder (tokens as a 1 x N map): producer / consumer kernel
-    (16, 512, 1, 200, 2048, True, 0, 1),
-    (3, 512, 1, 200, 2048, True, 0, None),     # few tokens: whatever the launcher picks
-    (2, 256, 7, 9, 96, False, 0, None),        # ragged pixels, HW % 4 != 0: scalar epilogues
+    (16, 512, 1, 200, 2048, True, 0, 1),       # 16 m-tiles x 25 pixel tiles >= 192
+    (3, 512, 1, 200, 2048, True, 0, 0),        # few tokens: 16 x 5 tiles < 192 and 32 x 10 narrow ones < 384; the DMA ring declines the flag
+    (2, 256, 7, 9, 96, False, 0, 0),           # ragged pixels, HW % 4 != 0: scalar epilogues of the generic kernel
     (2, 48, 16, 16, 72, True, 1, 0),           # short reduction: the generic kernel, accumulate on top
-    (2, 1824, 8, 8, 304, False, 0, None),      # few pixels, deep reduction: whatever the launcher picks must honour the flag (split-K tail)
+    (2, 1824, 8, 8, 304, False, 0, 0),         # few pixels, deep reduction: the generic kernel's split-K tail must honour the flag
 ])
 def test_conv1x1_times_gelu_grad_of_res(B, C1, H, W, M, bias, beta, want):
     """S2K_FLAG_RES_GELU_GRAD: Y = (conv + bias) * gelu'(RES) - fc2's data gradient through the GELU in one stage (plan/vit_plan.py
@@ -307,41 +321,48 @@ def test_conv3x3_bf16(B, C1, C2, H, W, M, pro, beta):
 
 
 @pytest.mark.parametrize("B,C1,H,W,M,pro,gate", [
-    (3, 24, 16, 16, 144, 0, False),      # expand 1x1, BM=32 config
-    (2, 144, 16, 16, 40, 2, True),       # project 1x1: BN+SiLU+SE gate prologue, BM=64
-    (2, 40, 12, 20, 240, 0, False),      # BM=128
-    (3, 304, 7, 7, 1824, 0, False),      # 7x7 maps: ragged pixel tail, HW=49
-    (2, 1824, 8, 8, 304, 2, True),       # deep project: small-problem 64x64 tiles, long K
-    (2, 32, 24, 24, 4, 3, False),        # out_conv1x1: M=4
+    (3, 24, 16, 16, 144, 0, False),      # expand 1x1, BM=32 config (18 tiles of 128 pixels, K = 24: neither pc nor DMA)
+    (2, 144, 16, 16, 40, 2, True),       # project 1x1: BN+SiLU+SE gate prologue, BM=64 (gate / SiLU: pc and DMA decline)
+    (2, 40, 12, 20, 240, 0, False),      # BM=128 (8 tiles, K = 40)
+    (3, 304, 7, 7, 1824, 0, False),      # 7x7 maps: ragged pixel tail, HW=49 (HW % 4 != 0: pc and DMA decline)
+    (2, 1824, 8, 8, 304, 2, True),       # deep project: small-problem 64x64 tiles, long K (gate)
+    (2, 32, 24, 24, 4, 3, False),        # out_conv1x1: M=4 (< 48 for pc, < 40 for DMA)
     (1, 13, 8, 8, 48, 0, False),         # K tail (13 channels)
 ])
 def test_conv1x1(B, C1, H, W, M, pro, gate):
-    _conv_case(B, C1, 0, H, W, M, 1, 1, 0, 0, H, W, pro, 0, gate, bias=(M == 4), stats=(M != 4))
+    """the generic kernel (csrc/igemm.hip): shapes that launch_conv_pc and launch_conv_dma decline"""
+    _conv_case(B, C1, 0, H, W, M, 1, 1, 0, 0, H, W, pro, 0, gate, bias=(M == 4), stats=(M != 4), want_variant=0)
 
 
 @pytest.mark.parametrize("B,C1,C2,H,W,M,pro1,pro2", [
-    (2, 40, 24, 20, 20, 64, 0, 0),      # decoder concat (up-conv output + skip), BM=64
-    (2, 32, 13, 32, 32, 32, 0, 0),      # input_double_conv.0: concat with the raw 13-band input
-    (2, 64, 0, 14, 14, 64, 3, 0),       # second conv of a double conv: BN+ReLU prologue; 14x14 (224 path)
-    (1, 88, 0, 28, 28, 128, 3, 0),      # BM=128
-    (1, 32, 0, 8, 72, 32, 3, 0),        # wide rows: row segments
-    (1, 16, 8, 40, 300, 32, 0, 0),      # width > tile: several x tiles per row
+    (2, 40, 24, 20, 20, 64, 0, 0),      # decoder concat (up-conv output + skip), BM=64 (W = 20: no producer / consumer tile geometry)
+    (2, 32, 13, 32, 32, 32, 0, 0),      # input_double_conv.0: concat with the raw 13-band input (thin, W % 64 != 0)
+    (2, 64, 0, 14, 14, 64, 3, 0),       # second conv of a double conv: BN+ReLU prologue; 14x14 (224 path) (4 tiles < 160)
+    (1, 88, 0, 28, 28, 128, 3, 0),      # BM=128 (7 tiles < 160)
+    (1, 32, 0, 8, 72, 32, 3, 0),        # wide rows: row segments (thin, W % 64 != 0)
+    (1, 16, 8, 40, 300, 32, 0, 0),      # width > tile: several x tiles per row (thin, W % 64 != 0)
 ])
 def test_conv3x3(B, C1, C2, H, W, M, pro1, pro2):
-    _conv_case(B, C1, C2, H, W, M, 3, 1, 1, 1, H, W, pro1, pro2, False, bias=True, stats=True)
+    """the generic kernel (csrc/igemm.hip): launch_conv_pc declines (reason per case)"""
+    _conv_case(B, C1, C2, H, W, M, 3, 1, 1, 1, H, W, pro1, pro2, False, bias=True, stats=True, want_variant=0)
 
 
-@pytest.mark.parametrize("B,C1,H,W,M,pro,bias,stats,beta", [
-    (4, 256, 64, 64, 256, 0, False, True, 0),    # 128 x 128 tiles, BatchNorm statistics epilogue
-    (4, 264, 64, 64, 200, 3, True, True, 0),     # 64-row tiles (M = 200 pads 128-row tiles by 28 %), ReLU prologue, bias, K tail (264 = 8 x 32 + 8)
-    (6, 288, 1, 200, 320, 0, True, False, 1),    # a Linear over feature-major tokens (H = 1), accumulate into Y (beta)
-    (3, 256, 100, 100, 176, 0, False, True, 0),  # pixel count not a multiple of the tile: tiles straddle images, ragged last tile
-    (4, 512, 32, 32, 384, 0, True, True, 0),     # 96 tiles of 128 x 128 would leave CUs empty: narrow 64 x 64 tiles (384 of them)
-    (6, 520, 26, 26, 512, 3, True, True, 0),     # narrow tiles, ReLU prologue, K tail, tiles straddle images (HW = 676)
-])
-def test_conv1x1_producer_consumer(B, C1, H, W, M, pro, bias, stats, beta):
-    """shapes that take the producer / consumer kernels (csrc/igemm_pc.hip): >= 192 tiles of 128 pixels"""
-    _conv_case(B, C1, 0, H, W, M, 1, 1, 0, 0, H, W, pro, 0, False, bias=bias, stats=stats, beta=beta)
+CONV1X1_PC = [   # (..., expected kernel family)
+    (4, 256, 64, 64, 256, 0, False, True, 0, 1),    # 128 x 128 tiles (2 x 128 >= 192, K >= 256), BatchNorm statistics epilogue
+    (4, 264, 64, 64, 200, 3, True, True, 0, 1),     # 64-row tiles (M = 200 pads 128-row tiles by 28 %: 4 x 128), ReLU prologue, bias, K tail (264 = 8 x 32 + 8)
+    (6, 288, 1, 200, 320, 0, True, False, 1, 0),    # a Linear over feature-major tokens (H = 1), accumulate into Y: 5 x 10 tiles < 192 and
+                                                    # K = 288 < 512 for narrow tiles (the DMA ring: K < 512, M < 768) - the generic kernel
+    (3, 256, 100, 100, 176, 0, False, True, 0, 1),  # pixel count not a multiple of the tile: tiles straddle images, ragged last tile (3 x 235)
+    (4, 512, 32, 32, 384, 0, True, True, 0, 1),     # 96 tiles of 128 x 128 would leave CUs empty: narrow 64 x 64 tiles (384 of them, K >= 512)
+    (6, 520, 26, 26, 512, 3, True, True, 0, 1),     # narrow tiles (8 x 64), ReLU prologue, K tail, tiles straddle images (HW = 676)
+]
+
+
+@pytest.mark.parametrize("B,C1,H,W,M,pro,bias,stats,beta,want", CONV1X1_PC, ids=_shape_ids(CONV1X1_PC, 9))
+def test_conv1x1_producer_consumer(B, C1, H, W, M, pro, bias, stats, beta, want):
+    """the producer / consumer kernels (csrc/igemm_pc.hip, launch_conv_pc) take >= 192 tiles of 128 pixels with K >= 256, or
+    >= 384 narrow 64 x 64 tiles with K >= 512; the case below those stays pinned to the generic kernel"""
+    _conv_case(B, C1, 0, H, W, M, 1, 1, 0, 0, H, W, pro, 0, False, bias=bias, stats=stats, beta=beta, want_variant=want)
 
 
 @pytest.mark.parametrize("B,C1,H,W,M,bias,stats,beta,res,scratch", [
@@ -387,20 +408,32 @@ def test_conv1x1_quad(B, C1, H, W, M, bias, stats, beta, res, scratch):
     _conv_case(B, C1, 0, H, W, M, 1, 1, 0, 0, H, W, 0, 0, False, bias=bias, stats=stats, beta=beta, res=res, scratch=scratch, want_variant=4)
 
 
-@pytest.mark.parametrize("B,C1,C2,H,W,M,pro,beta", [
-    (4, 40, 24, 64, 128, 64, 0, 0),      # (R, XW) = (2, 64): decoder concat conv, two x tiles per row
-    (8, 64, 0, 32, 32, 128, 3, 0),       # (4, 32): BatchNorm + ReLU prologue, zero padding after the activation
-    (20, 72, 0, 16, 16, 192, 3, 1),      # (8, 16): 64-row tiles x 3, accumulate (a data gradient on top of an existing one)
-    (4, 16, 8, 30, 56, 72, 0, 0),        # (2, 56) (224-pixel inputs), odd row count, K tail (24 channels = 3 chunks)
-    (12, 32, 0, 28, 28, 64, 3, 0),       # (4, 28)
-    (40, 64, 0, 14, 14, 128, 0, 0),      # (8, 14)
-    (32, 32, 13, 64, 64, 32, 0, 0),      # thin (M <= 32): 4 x 64 pixel tiles, consumers 1 x 4; concat with the raw input bands
-    (32, 32, 0, 64, 64, 32, 3, 0),       # thin, BatchNorm + ReLU prologue
-    (36, 64, 0, 62, 128, 24, 0, 1),      # thin, M = 24, ragged last tile row, accumulate
-])
-def test_conv3x3_producer_consumer(B, C1, C2, H, W, M, pro, beta):
+CONV3X3_PC = [   # (..., expected kernel family)
+    (4, 40, 24, 64, 128, 64, 0, 0, 1),      # (R, XW) = (2, 64): decoder concat conv, two x tiles per row (256 tiles)
+    (5, 64, 0, 32, 64, 256, 3, 0, 1),       # (2, 64), M >= 256: 8-channel chunks, two 128-row m-tiles (2 x 80 tiles)
+    (8, 64, 0, 32, 32, 128, 3, 0, 0),       # (4, 32) geometry but 64 tiles < 160: the generic kernel
+    (20, 64, 0, 32, 32, 128, 3, 0, 1),      # (4, 32): BatchNorm + ReLU prologue, zero padding after the activation (160 tiles)
+    (20, 72, 0, 16, 16, 192, 3, 1, 0),      # (8, 16) geometry but 3 x 40 tiles < 160: the generic kernel, accumulate
+    (40, 72, 0, 16, 16, 192, 3, 1, 1),      # (8, 16): 64-row tiles x 3, accumulate (a data gradient on top of an existing one) (3 x 80)
+    (4, 16, 8, 30, 56, 72, 0, 0, 0),        # (2, 56) geometry but 2 x 60 tiles < 160: the generic kernel, K tail (24 channels)
+    (12, 16, 8, 30, 56, 72, 0, 0, 1),       # (2, 56) (224-pixel inputs), odd row count, K tail (24 channels = 3 chunks) (2 x 180)
+    (4, 48, 0, 20, 112, 96, 3, 0, 1),       # (2, 56), two x tiles per row (2 x 80)
+    (12, 32, 0, 28, 28, 64, 3, 0, 0),       # (4, 28) geometry but 84 tiles < 160: the generic kernel
+    (24, 32, 0, 28, 28, 64, 3, 0, 1),       # (4, 28) (168 tiles)
+    (40, 64, 0, 14, 14, 128, 0, 0, 0),      # (8, 14) geometry but 80 tiles < 160: the generic kernel
+    (80, 64, 0, 14, 14, 128, 0, 0, 1),      # (8, 14) (160 tiles)
+    (32, 32, 13, 64, 64, 32, 0, 0, 1),      # thin (M <= 32): 4 x 64 pixel tiles (512 of them), consumers 1 x 4; concat with the raw input bands
+    (32, 32, 0, 64, 64, 32, 3, 0, 1),       # thin, BatchNorm + ReLU prologue
+    (36, 64, 0, 62, 128, 24, 0, 1, 1),      # thin, M = 24, ragged last tile row, accumulate
+]
+
+
+@pytest.mark.parametrize("B,C1,C2,H,W,M,pro,beta,want", CONV3X3_PC, ids=_shape_ids(CONV3X3_PC, 8))
+def test_conv3x3_producer_consumer(B, C1, C2, H, W, M, pro, beta, want):
+    """launch_conv_pc's 3x3 geometries: (R, XW) by the map width, taken when m-tiles x pixel tiles >= 160 (thin: >= 512 tiles);
+    each geometry also at a batch size just below that, which must stay on the generic kernel"""
     # (statistics + accumulate never occur together in a plan; the oracle takes the statistics before the accumulate)
-    _conv_case(B, C1, C2, H, W, M, 3, 1, 1, 1, H, W, pro, pro if C2 else 0, False, bias=True, stats=(beta == 0), beta=beta)
+    _conv_case(B, C1, C2, H, W, M, 3, 1, 1, 1, H, W, pro, pro if C2 else 0, False, bias=True, stats=(beta == 0), beta=beta, want_variant=want)
 
 
 @pytest.mark.parametrize("C,H,W", [(13, 32, 32), (6, 30, 26), (4, 64, 64)])
@@ -409,13 +442,13 @@ def test_stem_conv_tf_same_stride2(C, H, W):
 
     Ho, pt = same_pads(H, 3, 2)
     Wo, pl = same_pads(W, 3, 2)
-    _conv_case(2, C, 0, H, W, 48, 3, 2, pt, pl, Ho, Wo, 0, 0, False, bias=False, stats=True)
+    _conv_case(2, C, 0, H, W, 48, 3, 2, pt, pl, Ho, Wo, 0, 0, False, bias=False, stats=True, want_variant=0)     # stride 2: generic only
 
 
 @pytest.mark.parametrize("B,Cin,Cout,H,W,pro", [(2, 24, 16, 8, 8, 3), (1, 2048, 512, 2, 2, 2), (2, 64, 32, 16, 24, 3)])
 def test_conv_transpose_scatter(B, Cin, Cout, H, W, pro):
     _conv_case(B, Cin, 0, H, W, 4 * Cout, 1, 1, 0, 0, H, W, pro, 0, False, bias=True, stats=False,
-               mode=D.MODE_CONVT_SCATTER, strides=((Cin, Cout, 4), (1, 4 * Cout, 1)))
+               mode=D.MODE_CONVT_SCATTER, strides=((Cin, Cout, 4), (1, 4 * Cout, 1)), want_variant=0)     # scatter mode: generic only
 
 
 @pytest.mark.parametrize("B,Cin,Cout,H,W,pro", [(2, 24, 16, 8, 8, 3), (2, 2048, 512, 4, 4, 2), (2, 64, 32, 16, 24, 3)])
@@ -435,36 +468,54 @@ def test_conv_dgrad_3x3_flip(beta):
     pre, wp, MP = c.pack(wfull, Cs, Mout, 9, 9, Ctot * 9, 1, 1, src_elem_off=c_off * 9)
     c.run("CONV", ["y"], 1e-4, pre=[pre], X1=dy, BNV1=None, GATE1=None, X2=None, BNV2=None, WT=wp, BIAS=None, Y=y,
           STATS=None, B=B, C1=Mout, C2=0, H=H, W=W, M=Cs, KH=3, KW=3, STRIDE=1, PAD_T=1, PAD_L=1, HO=H, WO=W, PRO1=0,
-          PRO2=0, MODE=0, W_SM=1, W_SK=9 * MP, W_ST=MP, FLIP=0, BETA=beta, YC=Cs, NREP=1)
+          PRO2=0, MODE=0, W_SM=1, W_SK=9 * MP, W_ST=MP, FLIP=0, BETA=beta, YC=Cs, NREP=1, want_variant=0)   # thin, W % 64 != 0: generic
 
 
 def test_conv_dgrad_1x1_and_gather():
     _conv_case(2, 144, 0, 10, 10, 24, 1, 1, 0, 0, 10, 10, 0, 0, False, False, False, beta=1,
-               strides=((144, 24, 1), (1, 24, 1)))  # dgrad of an expand conv: A[c][m] = W[m][c]
+               strides=((144, 24, 1), (1, 24, 1)), want_variant=0)  # dgrad of an expand conv: A[c][m] = W[m][c] (M = 24: generic)
     # ConvTranspose dgrad: pseudo-channels (co,dy,dx) gathered from the 2x-resolution gradient
     _conv_case(2, 4 * 16, 0, 6, 10, 24, 1, 1, 0, 0, 6, 10, 0, 0, False, False, False, mode=D.MODE_GATHER2X2,
-               strides=((24, 16 * 4, 1), (64, 1, 1)))
+               strides=((24, 16 * 4, 1), (64, 1, 1)), want_variant=0)
 
 
 # ---------------------------------------------------------------------------------------------------
 # WGRAD
 # ---------------------------------------------------------------------------------------------------
-def _wgrad_case(B, M, C, CT, c_off, H, W, k, s, pt, pl, Ho, Wo, prop, proq, gateq, mode=0, seed=0, tol=2e-4, bf16=False):
+def _wgrad_case(B, M, C, CT, c_off, H, W, k, s, pt, pl, Ho, Wo, prop, proq, gateq, mode=0, seed=0, tol=2e-4, bf16=False,
+                want_variant=None, per_column=False, p_offset=0, bnq_scale=1.0):
     """bf16: FLAG_BF16 - the stage must run on csrc/wgrad_bf16.hip and is compared with the oracle on bf16-ROUNDED operands
-    (see _conv_case for the tolerance of stages with a prologue)."""
+    (see _conv_case for the tolerance of stages with a prologue).
+    want_variant: the kernel family the f32 stage must take (Case.run).
+    per_column: WGS starts at zero and Q channel c (and its BatchNorm shift) is scaled by 2^-(c mod 8) - an exact scaling, so the
+    sums and their rounding errors scale with their column - and every column of WGS is held to `tol` against its own max |ref|.
+    p_offset: P starts this many floats into its allocation (1: P is 4-byte aligned only).
+    bnq_scale: multiplies the BatchNorm scale of Q (large values drive the SiLU argument beyond the range of exp)."""
     c = Case(seed)
-    extra = dict(_flags=D.FLAG_BF16, want_variant=2) if bf16 else {}
+    extra = dict(_flags=D.FLAG_BF16, want_variant=2) if bf16 else dict(want_variant=want_variant)
     if bf16 and (prop or proq):
         tol = max(tol, 1e-3)
     T = k * k
-    P = c.t("p", (B, M, Ho, Wo))
-    Q = c.t("q", (B, C, H, W))
+    if p_offset:
+        P = c.t("p", (B * M * Ho * Wo + p_offset,)).at(p_offset, (B, M, Ho, Wo))
+    else:
+        P = c.t("p", (B, M, Ho, Wo))
+    colscale = 0.5 ** (torch.arange(C) % 8)
+    if per_column:
+        Q = c.t("q", (B, C, H, W), torch.randn(B, C, H, W, generator=c.gen) * colscale.view(1, C, 1, 1))
+    else:
+        Q = c.t("q", (B, C, H, W))
     bp = c.bnv("bnvp", M) if prop else None
     bq = c.bnv("bnvq", C) if proq else None
+    if proq and per_column:
+        c.items["bnvq"][1][1] *= colscale      # the BatchNorm shift too: u = scale * q + shift scales with its channel (ReLU exactly)
+    if proq and bnq_scale != 1.0:
+        c.items["bnvq"][1][0] *= bnq_scale
     gq = c.t("gateq", (B, C), "rand") if gateq else None
-    wgs = c.t("wgs", (T, M, CT), "randn")  # accumulates on top of existing content
-    c.run("WGRAD", ["wgs"], tol, P=P, BNVP=bp, GATEP=None, Q=Q, BNVQ=bq, GATEQ=gq, WGS=wgs.at(c_off), B=B, M=M, C=C,
-          CTOT=CT, H=H, W=W, KH=k, KW=k, STRIDE=s, PAD_T=pt, PAD_L=pl, HO=Ho, WO=Wo, PROP=prop, PROQ=proq, MODE=mode, **extra)
+    wgs = c.t("wgs", (T, M, CT), "zeros" if per_column else "randn")  # (randn: accumulates on top of existing content)
+    c.run("WGRAD", ["wgs"], tol, per_column=("wgs",) if per_column else (), P=P, BNVP=bp, GATEP=None, Q=Q, BNVQ=bq, GATEQ=gq,
+          WGS=wgs.at(c_off), B=B, M=M, C=C, CTOT=CT, H=H, W=W, KH=k, KW=k, STRIDE=s, PAD_T=pt, PAD_L=pl, HO=Ho, WO=Wo, PROP=prop,
+          PROQ=proq, MODE=mode, **extra)
 
 
 @pytest.mark.parametrize("B,M,C,H,W,prop,proq,gate", [
@@ -498,17 +549,136 @@ def test_wgrad_3x3_bf16(B, M, C, CT, c_off, H, W, proq):
     _wgrad_case(B, M, C, CT, c_off, H, W, 3, 1, 1, 1, H, W, 0, proq, False, bf16=True)
 
 
+# f32 1x1 / Linear weight gradients.  launch_wgrad tries, in this order: wgrad_q4_kernel (family 4: M, C > 32, H * W % 4 == 0,
+# 1024 <= B * H * W, P and Q 16-byte aligned, prologues (P, Q) in {(-, -), (-, ReLU), (ReLU, -), (-, SiLU [+ SE gate])}),
+# wgrad_pc_kernel's pixel mode (family 1: M, C > 32, B * H * W >= 1024, no gate, prologues (-, -), (-, ReLU), (ReLU, -)), then the
+# generic kernels (family 0).  Both faster kernels pick their tile by edge(n) per side: 128 where n > 64 and 128-channel tiles pad n
+# by at most 12 %, else 64 - (WM, WN) = (2, 2) for M 240 x C 250, (2, 1) for 240 x 144, (1, 2) for 144 x 240, (1, 1) for 40 x 176.
 @pytest.mark.parametrize("B,M,C,H,W,proq,gate", [(2, 40, 144, 16, 16, 2, True), (3, 144, 24, 12, 12, 0, False),
                                                    (2, 4, 32, 16, 16, 3, False), (3, 200, 130, 7, 7, 0, False)])
 def test_wgrad_1x1(B, M, C, H, W, proq, gate):
-    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, 0, proq, gate)
+    """the generic kernel: 512 pixels (< 1024), thin sides (<= 32 channels), 147 pixels with H * W % 4 != 0"""
+    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, 0, proq, gate, want_variant=0)
 
 
-@pytest.mark.parametrize("B,M,C,CT,c_off,H,W,proq", [(2, 64, 24, 64, 40, 20, 20, 0), (2, 32, 32, 32, 0, 24, 40, 3),
-                                                       (1, 32, 13, 45, 32, 32, 32, 0), (2, 128, 88, 88, 0, 14, 14, 3),
-                                                       (1, 48, 40, 40, 0, 9, 130, 0)])
-def test_wgrad_3x3(B, M, C, CT, c_off, H, W, proq):
-    _wgrad_case(B, M, C, CT, c_off, H, W, 3, 1, 1, 1, H, W, 0, proq, False)
+@pytest.mark.parametrize("B,M,C,H,W,prop,proq,gate", [
+    (5, 64, 64, 12, 17, 0, 0, False),        # B * H * W = 1020 (H * W % 4 == 0): below both kernels' 1024 pixels
+    (4, 32, 144, 16, 16, 0, 3, False),       # M = 32: thin, both decline
+])
+def test_wgrad_1x1_generic_tiles(B, M, C, H, W, prop, proq, gate):
+    """shapes that wgrad_q4_kernel and wgrad_pc_kernel decline (reason per case; more in test_wgrad_1x1_producer_consumer_tiles):
+    the generic kernel"""
+    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, prop, proq, gate, want_variant=0)
+
+
+@pytest.mark.parametrize("B,M,C,H,W,prop,proq,gate", [
+    # (WM, WN) = (2, 2): 128 x 128 tiles
+    (5, 240, 250, 16, 16, 0, 0, False),      # ragged on both sides, whole pixel tiles (1,280 pixels)
+    (5, 240, 250, 12, 20, 0, 3, False),      # ReLU on Q; 1,200 pixels: a partial last pixel tile (48 of 64)
+    (3, 240, 250, 20, 20, 3, 0, False),      # ReLU on P (ConvTranspose weight gradient form)
+    (6, 240, 250, 14, 14, 0, 2, False),      # SiLU on Q without a gate; H * W = 196: tiles straddle images, 24 pixels in the last tile
+    (11, 240, 250, 10, 10, 0, 2, True),      # SiLU + SE gate on Q; H * W = 100: the gate's image changes inside a pixel tile
+    (2, 768, 384, 1, 520, 0, 0, False),      # a Linear over feature-major tokens: H = 1, W = tokens
+    # (2, 1): 128 x 64
+    (4, 240, 144, 16, 16, 0, 0, False),      # B * H * W = 1024 exactly (16 pixel tiles)
+    (5, 240, 144, 12, 20, 0, 3, False),
+    (3, 240, 144, 20, 20, 3, 0, False),
+    (6, 240, 144, 14, 14, 0, 2, False),
+    (11, 240, 144, 10, 10, 0, 2, True),
+    # (1, 2): 64 x 128
+    (3, 144, 240, 20, 20, 0, 0, False),
+    (5, 144, 240, 12, 20, 0, 3, False),
+    (4, 144, 240, 16, 20, 3, 0, False),
+    (6, 144, 240, 14, 14, 0, 2, False),
+    (11, 144, 240, 10, 10, 0, 2, True),
+    # (1, 1): 64 x 64
+    (4, 40, 176, 16, 16, 0, 0, False),
+    (4, 40, 144, 16, 20, 0, 3, False),       # M = 40: one ragged 64-row tile, ReLU on Q
+    (4, 130, 130, 16, 16, 3, 0, False),      # 64-row tiles x 3, ReLU on P
+    (6, 40, 176, 14, 14, 0, 2, False),
+    (11, 40, 176, 10, 10, 0, 2, True),
+    (4, 33, 33, 16, 16, 0, 3, False),        # M = C = 33: the smallest sides it takes (31 rows / columns of the tile discarded)
+    (8, 64, 64, 64, 64, 0, 0, False),        # one output tile (mc = 1): 512 pixel tiles in 128 pixel splits
+    (8, 64, 64, 64, 64, 0, 2, True),         # the same with SiLU + SE gate
+    # production shapes
+    (32, 176, 1056, 16, 16, 0, 2, True),     # b5 U-Net, 16x16 MBConv project conv: SiLU + SE gate on Q, (1, 2)
+    (64, 2304, 768, 1, 52, 0, 0, False),     # MAE encoder qkv Linear, 3,328 tokens (padded to 52 per sample), (2, 2)
+    (64, 3072, 768, 1, 52, 0, 0, False),     # MAE encoder fc1 Linear, (2, 2)
+])
+def test_wgrad_1x1_quad(B, M, C, H, W, prop, proq, gate):
+    """wgrad_q4_kernel (csrc/wgrad_q4.hip): all 16 instantiations (4 tile geometries x 4 prologue forms)"""
+    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, prop, proq, gate, want_variant=4)
+
+
+@pytest.mark.parametrize("B,M,C,H,W,gate", [(11, 240, 250, 10, 10, True), (6, 40, 176, 14, 14, False)])
+def test_wgrad_1x1_quad_silu_beyond_exp_range(B, M, C, H, W, gate):
+    """Q's BatchNorm scale x 100: the SiLU argument u reaches hundreds, so e^-u overflows to inf in the producers' fast exp for
+    u < -88 (and 1 / (1 + inf) = 0): the result must stay finite and equal the oracle's SiLU"""
+    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, 0, D.PRO_SILU, gate, seed=38, want_variant=4, bnq_scale=100.0)
+
+
+WGRAD_1X1_PC = [   # (..., P's offset in floats, expected kernel family)
+    # shapes that wgrad_q4_kernel would take (see test_wgrad_1x1_quad), with P one float into its allocation: the quad kernel's
+    # 16-byte loads decline, wgrad_pc_kernel (one dword per load) takes them
+    (5, 240, 250, 16, 16, 0, 0, False, 1, 1),      # (2, 2): 128 x 128 tiles, ragged on both sides
+    (4, 40, 144, 16, 20, 0, 3, False, 1, 1),       # (1, 1) (M = 40: one ragged 64-row tile), ReLU on Q
+    (2, 768, 384, 1, 520, 0, 0, False, 1, 1),      # (2, 2), a Linear over feature-major tokens: H = 1, W = tokens
+    (4, 130, 130, 16, 16, 3, 0, False, 1, 1),      # (1, 1), 64-row tiles x 3, ReLU on P
+    # operands wgrad_pc_kernel has no instantiation for: the generic kernel
+    (22, 240, 72, 7, 7, 0, 2, True, 0, 0),         # SiLU + SE gate on Q (and H * W = 49: no quads either), images straddle tiles
+    (3, 64, 64, 20, 20, 2, 0, False, 0, 0),        # SiLU prologue on P (ConvTranspose weight gradient)
+    # H * W % 4 != 0 (7x7, 15x15, 13x21 maps) keeps wgrad_q4_kernel away; B * H * W >= 1024
+    (22, 240, 250, 7, 7, 0, 0, False, 0, 1),       # (2, 2), tiles straddle images
+    (5, 240, 250, 15, 15, 0, 3, False, 0, 1),
+    (4, 240, 250, 13, 21, 3, 0, False, 0, 1),
+    (5, 240, 144, 15, 15, 0, 0, False, 0, 1),      # (2, 1)
+    (4, 240, 144, 13, 21, 0, 3, False, 0, 1),
+    (22, 240, 144, 7, 7, 3, 0, False, 0, 1),
+    (4, 144, 240, 13, 21, 0, 0, False, 0, 1),      # (1, 2)
+    (22, 144, 240, 7, 7, 0, 3, False, 0, 1),
+    (5, 144, 240, 15, 15, 3, 0, False, 0, 1),
+    (22, 40, 176, 7, 7, 0, 0, False, 0, 1),        # (1, 1)
+    (5, 40, 176, 15, 15, 0, 3, False, 0, 1),
+    (4, 40, 176, 13, 21, 3, 0, False, 0, 1),
+    (32, 1824, 304, 7, 7, 0, 0, False, 0, 1),      # b5 U-Net on 224-pixel tiles, 7x7 expand conv, (2, 1)
+]
+
+
+@pytest.mark.parametrize("B,M,C,H,W,prop,proq,gate,p_offset,want", WGRAD_1X1_PC, ids=_shape_ids(WGRAD_1X1_PC, 8))
+def test_wgrad_1x1_producer_consumer_tiles(B, M, C, H, W, prop, proq, gate, p_offset, want):
+    """wgrad_pc_kernel's pixel mode (csrc/wgrad_pc.hip, launch_pc_pix): all 12 instantiations (4 tile geometries x 3 prologue pairs),
+    reached through a 4-byte-aligned P or H * W % 4 != 0; and the two operand forms it declines"""
+    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, prop, proq, gate, want_variant=want, p_offset=p_offset)
+
+
+@pytest.mark.parametrize("B,M,C,H,W,prop,proq,gate,want", [
+    (5, 240, 250, 12, 20, 0, 0, False, 4),   # quad (2, 2): the last c-tile holds 122 of 128 columns
+    (3, 240, 144, 20, 20, 3, 0, False, 4),   # quad (2, 1): 16 of 64
+    (11, 144, 240, 10, 10, 0, 2, True, 4),   # quad (1, 2), SiLU + gate: 112 of 128
+    (4, 40, 176, 16, 16, 0, 3, False, 4),    # quad (1, 1), ReLU: 48 of 64
+    (4, 33, 33, 16, 16, 0, 0, False, 4),     # quad, 33 of 64
+    (22, 240, 250, 7, 7, 0, 0, False, 1),    # pc (2, 2)
+    (5, 240, 144, 15, 15, 3, 0, False, 1),   # pc (2, 1)
+    (22, 40, 176, 7, 7, 0, 3, False, 1),     # pc (1, 1)
+    (22, 240, 72, 7, 7, 0, 2, True, 0),      # generic: 8 of 64
+])
+def test_wgrad_1x1_per_column(B, M, C, H, W, prop, proq, gate, want):
+    """ragged last channel tiles, each column held to 2e-4 of its own magnitude (Q channel c scaled by 2^-(c mod 8))"""
+    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, prop, proq, gate, seed=39, want_variant=want, per_column=True)
+
+
+WGRAD_3X3 = [   # (..., expected kernel family)
+    (2, 64, 24, 64, 40, 20, 20, 0, 0),      # thin (C <= 32) on a map narrower than 64: the generic kernel
+    (2, 32, 32, 32, 0, 24, 40, 3, 0),       # thin (M <= 32), W = 40: generic
+    (1, 32, 13, 45, 32, 32, 32, 0, 0),      # thin, W = 32: generic
+    (2, 128, 88, 88, 0, 14, 14, 3, 1),      # wgrad_pc (R, XWE) = (4, 14), ragged c tile
+    (1, 48, 40, 40, 0, 9, 130, 0, 1),       # wgrad_pc (1, 64), three x tiles per row (the last one 2 columns wide)
+]
+
+
+@pytest.mark.parametrize("B,M,C,CT,c_off,H,W,proq,want", WGRAD_3X3, ids=_shape_ids(WGRAD_3X3, 8))
+def test_wgrad_3x3(B, M, C, CT, c_off, H, W, proq, want):
+    _wgrad_case(B, M, C, CT, c_off, H, W, 3, 1, 1, 1, H, W, 0, proq, False, want_variant=want)
 
 
 @pytest.mark.parametrize("B,M,C,CT,c_off,H,W,proq", [
@@ -528,19 +698,7 @@ def test_wgrad_3x3(B, M, C, CT, c_off, H, W, proq):
 ])
 def test_wgrad_3x3_producer_consumer_tiles(B, M, C, CT, c_off, H, W, proq):
     """the shapes that take the producer / consumer kernels (csrc/wgrad_pc.hip), one case per compiled tile geometry"""
-    _wgrad_case(B, M, C, CT, c_off, H, W, 3, 1, 1, 1, H, W, 0, proq, False)
-
-
-@pytest.mark.parametrize("B,M,C,H,W,prop,proq,gate", [
-    (5, 240, 250, 16, 16, 0, 0, False),      # 128 x 128 tiles, ragged on both sides
-    (22, 240, 72, 7, 7, 0, 2, True),         # 128 x 64, SiLU + SE gate on Q, pixel count not a multiple of 64 (images straddle tiles)
-    (4, 40, 144, 16, 20, 0, 3, False),       # 64 x 128... (M = 40: one ragged 64-row tile), ReLU on Q
-    (3, 64, 64, 20, 20, 2, 0, False),        # 64 x 64, SiLU prologue on P (ConvTranspose weight gradient)
-    (2, 768, 384, 1, 520, 0, 0, False),      # a Linear over feature-major tokens: H = 1, W = tokens
-    (4, 130, 130, 16, 16, 3, 0, False),      # 64-row tiles x 3, ReLU on P
-])
-def test_wgrad_1x1_producer_consumer_tiles(B, M, C, H, W, prop, proq, gate):
-    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, prop, proq, gate)
+    _wgrad_case(B, M, C, CT, c_off, H, W, 3, 1, 1, 1, H, W, 0, proq, False, want_variant=1)
 
 
 def test_wgrad_stem_stride2():
@@ -549,12 +707,12 @@ def test_wgrad_stem_stride2():
     H, W = 32, 40
     Ho, pt = same_pads(H, 3, 2)
     Wo, pl = same_pads(W, 3, 2)
-    _wgrad_case(2, 48, 13, 13, 0, H, W, 3, 2, pt, pl, Ho, Wo, 0, 0, False)
+    _wgrad_case(2, 48, 13, 13, 0, H, W, 3, 2, pt, pl, Ho, Wo, 0, 0, False, want_variant=0)     # stride 2: generic only
 
 
 @pytest.mark.parametrize("B,Cin,Cout,H,W,prop", [(2, 64, 32, 8, 8, 3), (1, 200, 72, 4, 6, 2)])
 def test_wgrad_conv_transpose(B, Cin, Cout, H, W, prop):
-    _wgrad_case(B, Cin, Cout, Cout, 0, 2 * H, 2 * W, 2, 2, 0, 0, H, W, prop, 0, False, mode=D.MODE_GATHER2X2)
+    _wgrad_case(B, Cin, Cout, Cout, 0, 2 * H, 2 * W, 2, 2, 0, 0, H, W, prop, 0, False, mode=D.MODE_GATHER2X2, want_variant=0)
 
 
 def test_wgrad_finalize():
@@ -823,6 +981,7 @@ def test_conv_1x1_split_k(B, C, M, H, stats, beta, bias, bf16):
         extra = dict(WTB=wp16, _flags=D.FLAG_BF16, want_variant=2)
     else:
         pre, wp, MP = c.pack(w, M, C, 1, C, 1, 1, 0)
+        extra = dict(want_variant=0)      # SiLU prologue: the producer / consumer kernel and the DMA ring decline
     c.run("CONV", ["y"] + (["stats"] if stats else []), tol=1e-3 if bf16 else 1e-4, sum0=("stats",), pre=[pre], X1=x, BNV1=bnv, GATE1=None, X2=None,
           BNV2=None, WT=wp, BIAS=bs, Y=y, STATS=st, RES=None, SCRATCH=scratch, B=B, C1=C, C2=0, H=H, W=H, M=M, KH=1, KW=1, STRIDE=1,
           PAD_T=0, PAD_L=0, HO=H, WO=H, PRO1=D.PRO_SILU, PRO2=0, MODE=D.MODE_CONV, W_SM=1, W_SK=MP, W_ST=MP, FLIP=0, BETA=beta, YC=M,
@@ -848,7 +1007,7 @@ def test_conv3x3_reads_past_2gib():
     pre, wp, MP = c.pack(w, M, C, 9, C * 9, 9, 1, 0)
     c.run("CONV", ["y"], tol=1e-4, pre=[pre], X1=x, BNV1=None, GATE1=None, X2=None, BNV2=None, WT=wp, BIAS=None, Y=y, STATS=None, RES=None,
           B=B, C1=C, C2=0, H=H, W=H, M=M, KH=3, KW=3, STRIDE=1, PAD_T=1, PAD_L=1, HO=H, WO=H, PRO1=0, PRO2=0, MODE=D.MODE_CONV,
-          W_SM=1, W_SK=9 * MP, W_ST=MP, FLIP=0, BETA=0, YC=M, NREP=1)
+          W_SM=1, W_SK=9 * MP, W_ST=MP, FLIP=0, BETA=0, YC=M, NREP=1, want_variant=0)      # thin, W % 64 != 0: generic
 
 
 def test_convt_dgrad_gather_reads_past_2gib():
@@ -861,7 +1020,7 @@ def test_convt_dgrad_gather_reads_past_2gib():
     pre, wp, MP = c.pack(w, Cin, 4 * Cout, 1, 4 * Cout, 1, 1, 0)
     c.run("CONV", ["dx"], tol=1e-4, pre=[pre], X1=g, BNV1=None, GATE1=None, X2=None, BNV2=None, WT=wp, BIAS=None, Y=dx, STATS=None, RES=None,
           B=B, C1=4 * Cout, C2=0, H=H, W=H, M=Cin, KH=1, KW=1, STRIDE=1, PAD_T=0, PAD_L=0, HO=H, WO=H, PRO1=0, PRO2=0,
-          MODE=D.MODE_GATHER2X2, W_SM=1, W_SK=MP, W_ST=MP, FLIP=0, BETA=0, YC=Cin, NREP=1)
+          MODE=D.MODE_GATHER2X2, W_SM=1, W_SK=MP, W_ST=MP, FLIP=0, BETA=0, YC=Cin, NREP=1, want_variant=0)
 
 
 def test_wgrad3x3_reads_past_2gib():
@@ -872,7 +1031,7 @@ def test_wgrad3x3_reads_past_2gib():
     x = c.t("x", (B, C, H, H), scale=0.5)
     wgs = c.t("wgs", (9, M, C), "zeros")
     c.run("WGRAD", ["wgs"], tol=2e-4, P=dy, BNVP=None, GATEP=None, Q=x, BNVQ=None, GATEQ=None, WGS=wgs, B=B, M=M, C=C, CTOT=C, H=H, W=H,
-          KH=3, KW=3, STRIDE=1, PAD_T=1, PAD_L=1, HO=H, WO=H, PROP=0, PROQ=0, MODE=D.MODE_CONV)
+          KH=3, KW=3, STRIDE=1, PAD_T=1, PAD_L=1, HO=H, WO=H, PROP=0, PROQ=0, MODE=D.MODE_CONV, want_variant=0)    # thin, C > 32: generic
 
 
 @pytest.mark.parametrize("bf16", [False, True])
@@ -882,8 +1041,18 @@ def test_conv1x1_and_wgrad1x1_straddling_tiles_past_2gib(bf16):
     image each tile touches."""
     B, C, H, W, M = 15, 768, 220, 222, 8
     assert B * C * H * W * 4 > 2 ** 31 and (H * W) % 64 != 0 and (H * W) % 8 == 0
-    _conv_case(B, C, 0, H, W, M, 1, 1, 0, 0, H, W, D.PRO_NONE, 0, False, bias=False, stats=False, seed=35, bf16=bf16)
-    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, 0, 0, False, seed=36, bf16=bf16)
+    # (f32: M = 8 is below the producer / consumer, DMA-ring and quad kernels' thresholds - the generic kernels)
+    _conv_case(B, C, 0, H, W, M, 1, 1, 0, 0, H, W, D.PRO_NONE, 0, False, bias=False, stats=False, seed=35, bf16=bf16, want_variant=None if bf16 else 0)
+    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, 0, 0, False, seed=36, bf16=bf16, want_variant=0)
+
+
+@pytest.mark.parametrize("H,want", [(220, 4), (221, 1)])
+def test_wgrad1x1_quad_and_producer_consumer_past_2gib(H, want):
+    """the weight gradient above with M = 40 (> 32): on 220 x 222 (H * W % 4 == 0) wgrad_q4_kernel, whose descriptors are based at
+    the first of the two images a 64-pixel tile may touch; on 221 x 222 (H * W % 4 == 2) wgrad_pc_kernel's pixel mode"""
+    B, C, W, M = 15, 768, 222, 40
+    assert B * C * H * W * 4 > 2 ** 31 and (H * W) % 64 != 0 and (H * W) % 4 == (0 if want == 4 else 2)
+    _wgrad_case(B, M, C, C, 0, H, W, 1, 1, 0, 0, H, W, 0, 0, False, seed=37, want_variant=want)
 
 
 def test_convt_wgrad_gather_reads_past_2gib():
@@ -894,7 +1063,7 @@ def test_convt_wgrad_gather_reads_past_2gib():
     g = c.t("g", (B, Cout, H2, H2), scale=0.1)
     wgs = c.t("wgs", (4, Cin, Cout), "zeros")
     c.run("WGRAD", ["wgs"], tol=2e-4, P=xs, BNVP=None, GATEP=None, Q=g, BNVQ=None, GATEQ=None, WGS=wgs, B=B, M=Cin, C=Cout, CTOT=Cout,
-          H=H2, W=H2, KH=2, KW=2, STRIDE=2, PAD_T=0, PAD_L=0, HO=H, WO=H, PROP=0, PROQ=0, MODE=D.MODE_GATHER2X2)
+          H=H2, W=H2, KH=2, KW=2, STRIDE=2, PAD_T=0, PAD_L=0, HO=H, WO=H, PROP=0, PROQ=0, MODE=D.MODE_GATHER2X2, want_variant=0)
 
 
 @pytest.mark.parametrize("B,C,HW", [(2, 24, 256), (3, 10, 49), (1, 5, 4100), (6, 70, 64), (35, 9, 16), (4, 300, 36), (2, 6, 128 * 129)])
@@ -961,7 +1130,7 @@ def test_wgrad_1x1_with_prologue_on_p(B, M, C, H, pro):
     bnv = c.bnv("bnv", M) if pro else None
     wgs = c.t("wgs", (1, M, C), "zeros")
     c.run("WGRAD", ["wgs"], 2e-4, P=P, BNVP=bnv, GATEP=None, Q=Q, BNVQ=None, GATEQ=None, WGS=wgs, B=B, M=M, C=C, CTOT=C, H=H, W=H,
-          KH=1, KW=1, STRIDE=1, PAD_T=0, PAD_L=0, HO=H, WO=H, PROP=pro, PROQ=D.PRO_NONE, MODE=D.MODE_CONV)
+          KH=1, KW=1, STRIDE=1, PAD_T=0, PAD_L=0, HO=H, WO=H, PROP=pro, PROQ=D.PRO_NONE, MODE=D.MODE_CONV, want_variant=0)   # < 1024 pixels: generic
 
 
 @pytest.mark.parametrize("M,C,pro", [(4, 32, D.PRO_RELU), (24, 24, D.PRO_NONE), (32, 13, D.PRO_SILU)])
@@ -973,7 +1142,7 @@ def test_wgrad_1x1_thin_large_map(M, C, pro):
     bnv = c.bnv("bnv", C) if pro else None
     wgs = c.t("wgs", (1, M, C), "zeros")
     c.run("WGRAD", ["wgs"], 3e-4, P=P, BNVP=None, GATEP=None, Q=Q, BNVQ=bnv, GATEQ=None, WGS=wgs, B=B, M=M, C=C, CTOT=C, H=H, W=W,
-          KH=1, KW=1, STRIDE=1, PAD_T=0, PAD_L=0, HO=H, WO=W, PROP=D.PRO_NONE, PROQ=pro, MODE=D.MODE_CONV)
+          KH=1, KW=1, STRIDE=1, PAD_T=0, PAD_L=0, HO=H, WO=W, PROP=D.PRO_NONE, PROQ=pro, MODE=D.MODE_CONV, want_variant=0)   # thin: generic
 
 
 # ---------------------------------------------------------------------------------------------------
