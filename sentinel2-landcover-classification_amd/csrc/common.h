@@ -76,6 +76,24 @@ __device__ __forceinline__ float act_grad(float u, int act) {
 }
 
 // CONV epilogue with RES: v + r, or v * act'(r) when the stage carries S2K_FLAG_RES_GELU_GRAD (res_mul = the activation; kernel-uniform)
+// f32-SPLIT operands (S2K_FLAG_SPLIT): x = hi + mid + lo in three bf16 terms that hold all 24 significand bits - hi = bf16(x),
+// mid = bf16(x - hi), lo = bf16((x - hi) - mid), round-to-nearest-even, both differences exact in f32.  A non-finite hi keeps
+// mid = lo = 0 (x - hi would be NaN).  Non-finite operands therefore give non-finite outputs, but not always the f32 kernels' ones:
+// an Inf also meets the other operand's mid / lo terms, and where one of those is 0 or has the opposite sign the sum is NaN where
+// the f32 kernel gives +-Inf.  Two values per call: each output dword holds x0 in its low half and x1 in its high half (the packing
+// of v_cvt_pk_bf16_f32).
+__device__ __forceinline__ void split_bf16x2(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
+    typedef __bf16 sb16x2 __attribute__((ext_vector_type(2)));
+    typedef float sf32x2 __attribute__((ext_vector_type(2)));
+    const sf32x2 x = {x0, x1};
+    h = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, sb16x2));
+    const float h0 = __builtin_bit_cast(float, h << 16), h1 = __builtin_bit_cast(float, h & 0xffff0000u);
+    const sf32x2 r = {__builtin_isfinite(h0) ? x0 - h0 : 0.0f, __builtin_isfinite(h1) ? x1 - h1 : 0.0f};
+    m = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, sb16x2));
+    const sf32x2 q = {r[0] - __builtin_bit_cast(float, m << 16), r[1] - __builtin_bit_cast(float, m & 0xffff0000u)};
+    l = __builtin_bit_cast(uint32_t, __builtin_convertvector(q, sb16x2));
+}
+
 __device__ __forceinline__ float res_combine(float v, float r, int res_mul) { return res_mul ? v * act_grad(r, res_mul) : v + r; }
 
 // ---- bounds-checked buffer loads ----------------------------------------------------------------------

@@ -36,6 +36,16 @@ __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
 }
 
+// f32-SPLIT (common.h split_bf16x2): eight values -> the 16-byte units of the three planes hi / mid / lo
+__device__ __forceinline__ void split_unit(const float v[8], u32x4 w[3]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t h, m, l;
+        split_bf16x2(v[2 * k], v[2 * k + 1], h, m, l);
+        w[0][k] = h; w[1][k] = m; w[2][k] = l;
+    }
+}
+
 // 1x1 tiles: physical 16-byte slot of logical pixel slot s (a staging thread writes slots 4j .. 4j+3: without the swizzle the
 // eight lanes of a ds_write_b128 group hit two 16-byte columns of the 128-byte bank window, 4-way)
 __device__ __forceinline__ int swz(int s) { return s ^ ((s >> 3) & 3); }
@@ -45,10 +55,16 @@ __device__ __forceinline__ int swz(int s) { return s ^ ((s >> 3) & 3); }
 // X16 (no prologue, one source): X1 is stored as bf16 [B][C1][HW] (a BN_BWD_APPLY with OUT_BF16 wrote it): 1x1 - four pixels of a channel
 // are one 8-byte load; 3x3 - a halo element is one 16-bit load; the operand units are assembled from the halves - no conversion,
 // the values are the ones the f32 path would round to.
-template <int BMODE, int WVM, int WM, int WN, int KCH, int R, int XW, int PRO, bool GATE, bool SCATTER = false, bool X16 = false>
-__global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
+// SPLIT (the f32-SPLIT mode, S2K_FLAG_SPLIT): both operands as three bf16 planes (split_unit), each in the fragment layout above -
+// the weights from WEIGHT_PACK's SPLIT_BASE copy (planes hi / mid / lo of an entry one after the other), the activations split once
+// at staging time - and six MFMAs per k-step into the one accumulator, small terms first: mid*mid, hi*lo, lo*hi, hi*mid, mid*hi,
+// hi*hi (mid*lo, lo*mid, lo*lo are dropped: a few 2^-24 relative per product, the order of f32's own rounding).
+template <int BMODE, int WVM, int WM, int WN, int KCH, int R, int XW, int PRO, bool GATE, bool SCATTER = false, bool X16 = false, bool SPLIT = false>
+__global__ void __launch_bounds__(256, (SPLIT && BMODE != BM_PIX) ? 1 : 2) conv_bf16_kernel(const ConvP p) {     // (split 3x3: 133 KiB of LDS)
     constexpr bool PIX = BMODE == BM_PIX;
     static_assert(!X16 || (PRO == S2K_PRO_NONE && !GATE && !SCATTER), "bf16 X1: no prologue");
+    static_assert(!(X16 && SPLIT) && !(SPLIT && KCH > 64), "split: f32 operands, chunks of at most 64 channels");
+    constexpr int NPL = SPLIT ? 3 : 1;                       // operand planes
     constexpr int NT = 256;
     constexpr int WVN = 4 / WVM;
     constexpr int BM = WVM * WM * 32, BN = WVN * WN * 32;
@@ -66,9 +82,9 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
     static_assert(PIX || (!GATE && !SCATTER && (PRO == S2K_PRO_NONE || PRO == S2K_PRO_RELU)), "3x3: BatchNorm + ReLU prologue at most");
     static_assert(KCH <= 64 || PIX, "128-channel chunks: 1x1 only");
     extern __shared__ __attribute__((aligned(16))) u32x4 smem_b[];
-    u32x4* As = smem_b;
-    u32x4* Bs = smem_b + A_UNITS;
-    float* tab = reinterpret_cast<float*>(Bs + B_UNITS);     // [2][Ctp] scale / shift of every (concat) channel, zero beyond Ctot
+    u32x4* As = smem_b;                                      // [NPL][A_UNITS]
+    u32x4* Bs = smem_b + NPL * A_UNITS;                      // [NPL][B_UNITS]
+    float* tab = reinterpret_cast<float*>(Bs + NPL * B_UNITS);   // [2][Ctp] scale / shift of every (concat) channel, zero beyond Ctot
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int tile = xcd_remap(blockIdx.x, p.n_tiles);
@@ -87,6 +103,7 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
     const int MP = p.w_st;                                   // packed row count (M rounded up to 128)
     const u32x4* wsrc = reinterpret_cast<const u32x4*>(p.wtb);
     const int kp8 = ((p.Ctot + 63) / 64) * 8;                // octets of the packed K (WEIGHT_PACK pads K to a multiple of 64)
+    const int64_t wplane = (int64_t)kp8 * TT * MP;           // SPLIT: units between the weight planes of the entry
 
     // ---- staging geometry: fixed for the whole K loop ---------------------------------------------------------------------
     uint32_t bvoff[NBI];        // byte offset of the item's pixel quad / halo element in a channel plane (image-relative), or OOB
@@ -141,7 +158,7 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
         }
     }
 
-    u32x4 areg[NA];
+    u32x4 areg[NPL][NA];
     f32x4 bq[(PIX && !X16) ? NBI : 1][8];          // 1x1: eight channels x four pixels per item
     float2 bh[X16 ? NBI : 1][8];                   // X16: the same as four bf16 (two dwords) per channel
     float bs[PIX ? 1 : NBI][8];          // 3x3: eight channels of one halo element per item
@@ -158,9 +175,11 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
                 // the packed K is a multiple of 64: the upper half of the last 128-channel chunk may lie past the entry - re-read its
                 // last octet (the matching B units are zeroed at the commit)
                 const int o = min(ob0 + ot / TT, kp8 - 1), tap = ot % TT;
-                if (A_UNITS % NT == 0 || u < A_UNITS) areg[i] = wsrc[((int64_t)o * TT + tap) * MP + m0 + row];
+                if (A_UNITS % NT == 0 || u < A_UNITS) areg[0][i] = wsrc[((int64_t)o * TT + tap) * MP + m0 + row];
             } else {
-                if (A_UNITS % NT == 0 || u < A_UNITS) areg[i] = wsrc[((int64_t)ob0 * TT + ot) * MP + m0 + row];
+                if (A_UNITS % NT == 0 || u < A_UNITS)
+#pragma unroll
+                    for (int pl = 0; pl < NPL; ++pl) areg[pl][i] = wsrc[pl * wplane + ((int64_t)ob0 * TT + ot) * MP + m0 + row];
             }
         }
         if (PIX) {
@@ -190,7 +209,9 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int u = tid + NT * i;
-            if (A_UNITS % NT == 0 || u < A_UNITS) As[u] = areg[i];
+            if (A_UNITS % NT == 0 || u < A_UNITS)
+#pragma unroll
+                for (int pl = 0; pl < NPL; ++pl) As[pl * A_UNITS + u] = areg[pl][i];
         }
 #pragma unroll
         for (int i = 0; i < NBI; ++i) {
@@ -231,10 +252,17 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
                         if (GATE) x *= greg[(PIX && GATE) ? i : 0][q];
                         v[q] = x;
                     }
-                    u32x4 w = {pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7])};
-                    if constexpr (KCH > 64) { if (c0 + 8 * b_co[i] >= 8 * kp8) w = u32x4{0u, 0u, 0u, 0u}; }    // octets past the packed K
                     const int s = (b_dst[i] % BN) + e;
-                    Bs[(b_dst[i] - (b_dst[i] % BN)) + swz(s)] = w;
+                    if constexpr (SPLIT) {
+                        u32x4 w[3];
+                        split_unit(v, w);
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl) Bs[pl * B_UNITS + (b_dst[i] - (b_dst[i] % BN)) + swz(s)] = w[pl];
+                    } else {
+                        u32x4 w = {pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7])};
+                        if constexpr (KCH > 64) { if (c0 + 8 * b_co[i] >= 8 * kp8) w = u32x4{0u, 0u, 0u, 0u}; }    // octets past the packed K
+                        Bs[(b_dst[i] - (b_dst[i] % BN)) + swz(s)] = w;
+                    }
                 }
             } else if constexpr (X16) {
                 uint32_t hb[8];
@@ -249,8 +277,15 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
                     if (PRO == S2K_PRO_RELU) x = __builtin_amdgcn_fmed3f(fmaf(x, sc[q], sh[q]), 0.0f, bound[PIX ? 0 : i]);   // the reference pads ACTIVATED maps
                     v[q] = x;
                 }
-                u32x4 w = {pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7])};
-                Bs[b_dst[i]] = w;
+                if constexpr (SPLIT) {
+                    u32x4 w[3];
+                    split_unit(v, w);
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) Bs[pl * B_UNITS + b_dst[i]] = w[pl];
+                } else {
+                    u32x4 w = {pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7])};
+                    Bs[b_dst[i]] = w;
+                }
             }
         }
     };
@@ -284,18 +319,29 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
             const int toff = PIX ? 0 : (tap / 3) * WS + (tap % 3);
 #pragma unroll
             for (int s = 0; s < NO / 2; ++s) {
-                bf16x8 a[WM], b[WN];
+                bf16x8 a[NPL][WM], b[NPL][WN];
 #pragma unroll
-                for (int rm = 0; rm < WM; ++rm)
-                    a[rm] = __builtin_bit_cast(bf16x8, As[((2 * s) * TT + tap) * BM + lh * (TT * BM) + wm0 + rm * 32 + l31]);
+                for (int pl = 0; pl < NPL; ++pl) {
 #pragma unroll
-                for (int rn = 0; rn < WN; ++rn)
-                    b[rn] = __builtin_bit_cast(bf16x8, Bs[(2 * s) * USED + lh * USED + bslot[rn] + toff]);
-#pragma unroll
-                for (int rm = 0; rm < WM; ++rm)
+                    for (int rm = 0; rm < WM; ++rm)
+                        a[pl][rm] = __builtin_bit_cast(bf16x8, As[pl * A_UNITS + ((2 * s) * TT + tap) * BM + lh * (TT * BM) + wm0 + rm * 32 + l31]);
 #pragma unroll
                     for (int rn = 0; rn < WN; ++rn)
-                        acc[rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rm], b[rn], acc[rm][rn], 0, 0, 0);
+                        b[pl][rn] = __builtin_bit_cast(bf16x8, Bs[pl * B_UNITS + (2 * s) * USED + lh * USED + bslot[rn] + toff]);
+                }
+#pragma unroll
+                for (int rm = 0; rm < WM; ++rm)
+#pragma unroll
+                    for (int rn = 0; rn < WN; ++rn) {
+                        if constexpr (SPLIT) {      // plane 0 = hi, 1 = mid, 2 = lo; small terms first
+                            acc[rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][rm], b[1][rn], acc[rm][rn], 0, 0, 0);
+                            acc[rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][rm], b[2][rn], acc[rm][rn], 0, 0, 0);
+                            acc[rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][rm], b[0][rn], acc[rm][rn], 0, 0, 0);
+                            acc[rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][rm], b[1][rn], acc[rm][rn], 0, 0, 0);
+                            acc[rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][rm], b[0][rn], acc[rm][rn], 0, 0, 0);
+                        }
+                        acc[rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][rm], b[0][rn], acc[rm][rn], 0, 0, 0);
+                    }
             }
         }
         __syncthreads();                                         // every wave is done reading the image
@@ -483,7 +529,7 @@ __global__ void __launch_bounds__(256, 2) conv_bf16_kernel(const ConvP p) {
 }
 
 // -------------------------------------------------------------------------------------------------
-template <int BMODE, int WVM, int WM, int WN, int KCH, int R, int XW, int PRO, bool GATE, bool SCATTER = false, bool X16 = false>
+template <int BMODE, int WVM, int WM, int WN, int KCH, int R, int XW, int PRO, bool GATE, bool SCATTER = false, bool X16 = false, bool SPLIT = false>
 static int launch_b16(ConvP& p, int n_ntiles, hipStream_t st) {
     constexpr bool PIX = BMODE == BM_PIX;
     constexpr int WVN = 4 / WVM;
@@ -491,14 +537,17 @@ static int launch_b16(ConvP& p, int n_ntiles, hipStream_t st) {
     constexpr int TT = PIX ? 1 : 9;
     constexpr int NO = KCH / 8;
     constexpr int USED = PIX ? BN : (R + 2) * (XW + 2);
-    constexpr size_t img = (size_t)(NO * TT * BM + NO * USED) * 16;
+    constexpr size_t img = (size_t)(NO * TT * BM + NO * USED) * 16 * (SPLIT ? 3 : 1);
     static_assert(img <= 160 * 1024, "LDS image");
     static_assert((size_t)WVN * 2 * BM * sizeof(float) <= img, "statistics rows fit in the image");
     p.n_mtiles = cdiv(p.M, BM);
     const int nchunks = cdiv(p.Ctot, KCH);
     constexpr size_t ct_bytes = (!SCATTER && (PIX || XW % 4 == 0)) ? (size_t)WVM * 32 * (BN + 8) * sizeof(float) : 0;   // transposed store
     const size_t lds = std::max(img + (PRO != S2K_PRO_NONE ? (size_t)2 * nchunks * KCH * sizeof(float) : 0), ct_bytes);
-    if (lds > 160 * 1024) return 1;
+    if (lds > 160 * 1024) {
+        if (SPLIT) { set_error("conv: f32-split stage needs %zu B of LDS (prologue table of %d channels)", lds, p.Ctot); return S2K_EINVAL; }
+        return 1;
+    }
     {   // 32-bit buffer offsets: image-local tiles need one image < 2 GiB, tiles that may straddle images the whole tensor
         // (descriptors are based at the first image a tile touches)
         const int64_t span = (!PIX || (p.HW % BN) == 0) ? 1 : std::min<int64_t>(p.B, (BN - 2) / p.HW + 2);
@@ -524,39 +573,43 @@ static int launch_b16(ConvP& p, int n_ntiles, hipStream_t st) {
             p.splits = cdiv(nchunks, p.chunks_per_split);
         }
     }
-    auto kern = conv_bf16_kernel<BMODE, WVM, WM, WN, KCH, R, XW, PRO, GATE, SCATTER, X16>;
+    auto kern = conv_bf16_kernel<BMODE, WVM, WM, WN, KCH, R, XW, PRO, GATE, SCATTER, X16, SPLIT>;
     static PerDeviceOnce attr_once;
     attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)p.splits), dim3(256), lds, st, p);
     if (p.splits > 1) launch_splitk_reduce(p, st);
-    g_s2k_variant = 2;
+    g_s2k_variant = SPLIT ? 5 : 2;
     return S2K_OK;
 }
 
 // tile height by M: 64 rows when 128 would pad M by more than 12 % (32-row tiles, 1 x 4 waves over 256 pixels, are instantiated
 // by the callers: their pixel tile differs)
-template <int BMODE, int KCH, int R, int XW, int PRO, bool GATE, bool SCATTER = false, bool X16 = false>
+template <int BMODE, int KCH, int R, int XW, int PRO, bool GATE, bool SCATTER = false, bool X16 = false, bool SPLIT = false>
 static int launch_b16_bm(ConvP& p, int n128, hipStream_t st) {
     if (p.M <= 32) return 1;
     const bool big = p.M > 64 && (double)cdiv(p.M, 128) * 128 / p.M <= 1.12;
-    if (big) return launch_b16<BMODE, 2, 2, 2, KCH, R, XW, PRO, GATE, SCATTER, X16>(p, n128, st);
-    return launch_b16<BMODE, 2, 1, 2, KCH, R, XW, PRO, GATE, SCATTER, X16>(p, n128, st);
+    if (big) return launch_b16<BMODE, 2, 2, 2, KCH, R, XW, PRO, GATE, SCATTER, X16, SPLIT>(p, n128, st);
+    return launch_b16<BMODE, 2, 1, 2, KCH, R, XW, PRO, GATE, SCATTER, X16, SPLIT>(p, n128, st);
 }
 
-template <int KCH, int PRO, bool GATE, bool X16 = false>
+template <int KCH, int PRO, bool GATE, bool X16 = false, bool SPLIT = false>
 static int launch_b16_pix(ConvP& p, hipStream_t st) {
     if constexpr (KCH <= 64) {
-        if (p.M <= 32) return launch_b16<BM_PIX, 1, 1, 2, KCH, 1, 64, PRO, GATE, false, X16>(p, cdiv(p.Ntot, 256), st);
+        if (p.M <= 32) return launch_b16<BM_PIX, 1, 1, 2, KCH, 1, 64, PRO, GATE, false, X16, SPLIT>(p, cdiv(p.Ntot, 256), st);
     }
     // few pixels (the 8 x 8 / 16 x 16 maps of the deep blocks): 128-pixel tiles would leave most CUs without a workgroup and each
     // of the few with a long serial K loop; 64 x 64 tiles give 4x the workgroups
     const int n128 = cdiv(p.Ntot, 128);
-    if ((int64_t)n128 * cdiv(p.M, 128) < 200) return launch_b16<BM_PIX, 2, 1, 1, KCH, 1, 64, PRO, GATE, false, X16>(p, cdiv(p.Ntot, 64), st);
-    return launch_b16_bm<BM_PIX, KCH, 1, 64, PRO, GATE, false, X16>(p, n128, st);
+    if ((int64_t)n128 * cdiv(p.M, 128) < 200) return launch_b16<BM_PIX, 2, 1, 1, KCH, 1, 64, PRO, GATE, false, X16, SPLIT>(p, cdiv(p.Ntot, 64), st);
+    return launch_b16_bm<BM_PIX, KCH, 1, 64, PRO, GATE, false, X16, SPLIT>(p, n128, st);
 }
 
-// S2K_OK = launched, 1 = not one of its shapes (the caller takes the f32 kernels), < 0 = error
-int launch_conv_bf16(ConvP& p, hipStream_t st) {
+// The shape lists of both modes.  SPLIT holds three operand planes in LDS, so its chunks are half as deep: 1x1 32 channels
+// (64 for the deep reductions; a 128 x 128 tile's image is then 48 / 96 KiB), 3x3 16 channels as in bf16-mixed (133 KiB at
+// 128 x 128: one workgroup per CU).  S2K_OK = launched, 1 = not one of its shapes, < 0 = error
+template <bool SPLIT>
+static int conv_b16_route(ConvP& p, hipStream_t st) {
+    constexpr int K1 = SPLIT ? 32 : 64, KDEEP = SPLIT ? 64 : 128;
     if (!p.wtb || p.S != 1 || p.HO != p.H || p.WO != p.W) return 1;
     const int T = p.KH * p.KW;
     if (p.x1_bf16 && p.mode != S2K_MODE_CONV) return 1;
@@ -564,8 +617,8 @@ int launch_conv_bf16(ConvP& p, hipStream_t st) {
         // ConvTranspose2d(k2, s2) forward: a 1x1 contraction with rows (co, dy, dx) and a scattering epilogue
         if (T != 1 || p.C2 != 0 || (p.HW & 3) || p.gate1 || p.M <= 32 || (p.M & 3)) return 1;
         const int n128 = cdiv(p.Ntot, 128);
-        if (p.pro1 == S2K_PRO_RELU) return launch_b16_bm<BM_PIX, 64, 1, 64, S2K_PRO_RELU, false, true>(p, n128, st);
-        if (p.pro1 == S2K_PRO_SILU) return launch_b16_bm<BM_PIX, 64, 1, 64, S2K_PRO_SILU, false, true>(p, n128, st);
+        if (p.pro1 == S2K_PRO_RELU) return launch_b16_bm<BM_PIX, K1, 1, 64, S2K_PRO_RELU, false, true, false, SPLIT>(p, n128, st);
+        if (p.pro1 == S2K_PRO_SILU) return launch_b16_bm<BM_PIX, K1, 1, 64, S2K_PRO_SILU, false, true, false, SPLIT>(p, n128, st);
         return 1;
     }
     if (p.mode != S2K_MODE_CONV) return 1;
@@ -578,18 +631,18 @@ int launch_conv_bf16(ConvP& p, hipStream_t st) {
         // 4 - 8 % to the larger LDS image, so only problems of at most 1,024 128 x 128 tiles take it; the 32-row tile would spill)
         const bool deep = p.Ctot >= deep_min && p.M > 32 && (int64_t)cdiv(p.Ntot, 128) * cdiv(p.M, 128) <= 1024;
         if (p.gate1) {
-            if (p.pro1 == S2K_PRO_SILU) return deep ? launch_b16_pix<128, S2K_PRO_SILU, true>(p, st) : launch_b16_pix<64, S2K_PRO_SILU, true>(p, st);
+            if (p.pro1 == S2K_PRO_SILU) return deep ? launch_b16_pix<KDEEP, S2K_PRO_SILU, true, false, SPLIT>(p, st) : launch_b16_pix<K1, S2K_PRO_SILU, true, false, SPLIT>(p, st);
             return 1;
         }
-        if (p.x1_bf16) {      // X1 stored as bf16 (opdefs CONV.X1_BF16): planned only for this shape class; nothing else reads such a tensor
+        if (!SPLIT && p.x1_bf16) {      // X1 stored as bf16 (opdefs CONV.X1_BF16): planned only for this shape class; nothing else reads such a tensor
             if (p.gate1 || p.pro1 != S2K_PRO_NONE || (p.HW & 7)) { set_error("conv: X1_BF16 is for plain 1x1 stages (no prologue, H*W % 8 == 0)"); return S2K_EINVAL; }
-            return deep ? launch_b16_pix<128, S2K_PRO_NONE, false, true>(p, st) : launch_b16_pix<64, S2K_PRO_NONE, false, true>(p, st);
+            if constexpr (!SPLIT) return deep ? launch_b16_pix<128, S2K_PRO_NONE, false, true>(p, st) : launch_b16_pix<64, S2K_PRO_NONE, false, true>(p, st);
         }
         switch (p.pro1) {
-            case S2K_PRO_NONE: return deep ? launch_b16_pix<128, S2K_PRO_NONE, false>(p, st) : launch_b16_pix<64, S2K_PRO_NONE, false>(p, st);
-            case S2K_PRO_RELU: return launch_b16_pix<64, S2K_PRO_RELU, false>(p, st);
-            case S2K_PRO_SILU: return launch_b16_pix<64, S2K_PRO_SILU, false>(p, st);
-            case S2K_PRO_AFFINE: return launch_b16_pix<64, S2K_PRO_AFFINE, false>(p, st);
+            case S2K_PRO_NONE: return deep ? launch_b16_pix<KDEEP, S2K_PRO_NONE, false, false, SPLIT>(p, st) : launch_b16_pix<K1, S2K_PRO_NONE, false, false, SPLIT>(p, st);
+            case S2K_PRO_RELU: return launch_b16_pix<K1, S2K_PRO_RELU, false, false, SPLIT>(p, st);
+            case S2K_PRO_SILU: return launch_b16_pix<K1, S2K_PRO_SILU, false, false, SPLIT>(p, st);
+            case S2K_PRO_AFFINE: return launch_b16_pix<K1, S2K_PRO_AFFINE, false, false, SPLIT>(p, st);
             default: return 1;
         }
     }
@@ -605,15 +658,15 @@ int launch_conv_bf16(ConvP& p, hipStream_t st) {
     };
     const bool relu = p.pro1 == S2K_PRO_RELU;
 #define B16_3X3(RR, XX) { const int n = tiles(RR, XX); \
-        if (p.x1_bf16) return launch_b16_bm<BM_SPATIAL, 16, RR, XX, S2K_PRO_NONE, false, false, true>(p, n, st); \
-        return relu ? launch_b16_bm<BM_SPATIAL, 16, RR, XX, S2K_PRO_RELU, false>(p, n, st) \
-                    : launch_b16_bm<BM_SPATIAL, 16, RR, XX, S2K_PRO_NONE, false>(p, n, st); }
+        if (!SPLIT && p.x1_bf16) return launch_b16_bm<BM_SPATIAL, 16, RR, XX, S2K_PRO_NONE, false, false, !SPLIT>(p, n, st); \
+        return relu ? launch_b16_bm<BM_SPATIAL, 16, RR, XX, S2K_PRO_RELU, false, false, false, SPLIT>(p, n, st) \
+                    : launch_b16_bm<BM_SPATIAL, 16, RR, XX, S2K_PRO_NONE, false, false, false, SPLIT>(p, n, st); }
     if (p.M <= 32) {
         if (p.WO < 64 || p.WO % 64 != 0) return 1;
         const int n = tiles(4, 64);
-        if (p.x1_bf16) return launch_b16<BM_SPATIAL, 1, 1, 2, 16, 4, 64, S2K_PRO_NONE, false, false, true>(p, n, st);
-        return relu ? launch_b16<BM_SPATIAL, 1, 1, 2, 16, 4, 64, S2K_PRO_RELU, false>(p, n, st)
-                    : launch_b16<BM_SPATIAL, 1, 1, 2, 16, 4, 64, S2K_PRO_NONE, false>(p, n, st);
+        if (!SPLIT && p.x1_bf16) return launch_b16<BM_SPATIAL, 1, 1, 2, 16, 4, 64, S2K_PRO_NONE, false, false, !SPLIT>(p, n, st);
+        return relu ? launch_b16<BM_SPATIAL, 1, 1, 2, 16, 4, 64, S2K_PRO_RELU, false, false, false, SPLIT>(p, n, st)
+                    : launch_b16<BM_SPATIAL, 1, 1, 2, 16, 4, 64, S2K_PRO_NONE, false, false, false, SPLIT>(p, n, st);
     }
     if (p.WO >= 64 && p.WO % 64 == 0) B16_3X3(2, 64)
     if (p.WO == 32) B16_3X3(4, 32)
@@ -623,6 +676,19 @@ int launch_conv_bf16(ConvP& p, hipStream_t st) {
     if (p.WO == 14) B16_3X3(8, 14)
 #undef B16_3X3
     return 1;
+}
+
+// bf16-mixed: S2K_OK = launched, 1 = not one of its shapes (the caller takes the f32 kernels), < 0 = error
+int launch_conv_bf16(ConvP& p, hipStream_t st) { return conv_b16_route<false>(p, st); }
+
+// f32-split (S2K_FLAG_SPLIT): S2K_OK = launched, < 0 = error.  A split stage never falls back - neither to the bf16-rounded kernels
+// nor to an f32 kernel: the planner flags only the shapes listed above (plan/split.py), anything else is an error.
+int launch_conv_split(ConvP& p, hipStream_t st) {
+    if (!p.wtb) { set_error("conv: f32-split stage without the split weight copy (WTB)"); return S2K_EINVAL; }
+    if (p.x1_bf16) { set_error("conv: f32-split stages read f32 operands (X1_BF16 set)"); return S2K_EINVAL; }
+    const int rc = conv_b16_route<true>(p, st);
+    if (rc == 1) { set_error("conv: f32-split stage with a shape the split kernels do not take (plan/split.py)"); return S2K_EINVAL; }
+    return rc;
 }
 
 }  // namespace s2k

@@ -180,6 +180,36 @@ __global__ void __launch_bounds__(NTHREADS) weight_pack_bf16_kernel(const int* t
     dst16[(r[1] >> 3) + v] = w;                                   // ushort offset r[1] of the bf16 region = unit r[1] / 8
 }
 
+// f32-split plans: every packed entry as three bf16 planes hi / mid / lo (common.h split_bf16x2), each plane an entry-sized copy in
+// the fragment order of weight_pack_bf16_kernel, the three one after the other: the entry at f32 offset r[1] starts at unit
+// 3 * r[1] / 8 of the region (csrc/conv_bf16.hip, SPLIT, reads plane p at + p * (entry units)).
+__global__ void __launch_bounds__(NTHREADS) weight_pack_split_kernel(const int* table, int n_entries, const float* packed, uint4* dst16) {
+    const int64_t e0 = (int64_t)blockIdx.x * (NTHREADS * 8);       // first f32 element of this block's units
+    int lo = 0, hi = n_entries - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((int64_t)table[mid * 12 + 11] <= e0) lo = mid; else hi = mid - 1;
+    }
+    const int* r = table + lo * 12;
+    const int T = r[4], MP = r[9], KP = r[10];
+    const int64_t v = ((e0 - r[11]) >> 3) + threadIdx.x;           // unit inside the entry: (ob * T + tap) * MP + m
+    const int m = (int)(v % MP);
+    const int64_t ot = v / MP;
+    const int tap = (int)(ot % T);
+    const int64_t ob = ot / T;
+    const float* sp = packed + r[1];
+    float x[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) x[q] = sp[((ob * 8 + q) * T + tap) * MP + m];
+    uint32_t w[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) split_bf16x2(x[2 * k], x[2 * k + 1], w[0][k], w[1][k], w[2][k]);
+    const int64_t units = (int64_t)KP * T * MP / 8;                // one plane of the entry
+    uint4* dp = dst16 + 3 * ((int64_t)r[1] >> 3) + v;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) dp[pl * units] = make_uint4(w[pl][0], w[pl][1], w[pl][2], w[pl][3]);
+}
+
 // f32 plans: a second copy of every 1x1 entry (T = 1) in the "quad" layout of csrc/conv_q4.hip, [KP/8][MP][8] with the eight input
 // channels of a group in the order (k & 1) * 4 + (k >> 1): the A operands of four consecutive MFMA k-steps (k = 2 s + lane / 32)
 // are then 16 contiguous bytes of LDS.  Reads the f32 pack the kernel above has just written (L2-hot, lanes along m), two 16-byte
@@ -229,6 +259,12 @@ int launch_weight_pack(const S2kOp& op, const Ctx& c) {
         if (q4 & 15) { set_error("weight_pack: Q4_BASE must be a multiple of 16 bytes"); return S2K_EINVAL; }
         hipLaunchKernelGGL(weight_pack_q4_kernel, dim3((unsigned)(total / (NTHREADS * 8))), dim3(NTHREADS), 0, c.stream, table, n,
                            dst, reinterpret_cast<float*>(reinterpret_cast<char*>(dst) + q4));
+    }
+    const int64_t sb = op.n[S2K_WEIGHT_PACK_N_SPLIT_BASE];
+    if (sb > 0) {
+        if (sb & 15) { set_error("weight_pack: SPLIT_BASE must be a multiple of 16 bytes"); return S2K_EINVAL; }
+        hipLaunchKernelGGL(weight_pack_split_kernel, dim3((unsigned)(total / (NTHREADS * 8))), dim3(NTHREADS), 0, c.stream, table, n,
+                           dst, reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + sb));
     }
     return S2K_OK;
 }

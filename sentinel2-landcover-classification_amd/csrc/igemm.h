@@ -14,7 +14,8 @@ struct ConvP {
     int res_mul;         // S2K_FLAG_RES_GELU_GRAD: the epilogue multiplies by act'(RES) (= S2K_PRO_GELU) instead of adding RES; else 0
     int force_dma;       // S2K_FLAG_DMA: the LDS-DMA ring kernel for every shape it supports (tests), not only where its routing rule sends a stage
     int exp;             // tuning builds only (S2K_CV_EXP): 1 = no epilogue (nothing stored), 2 = no MFMA loop
-    const void* wtb;     // bf16 copy of the packed weights ([KP/8][T][MP][8], WEIGHT_PACK BF16_BASE) when the stage carries S2K_FLAG_BF16, else null
+    const void* wtb;     // bf16 copy of the packed weights ([KP/8][T][MP][8], WEIGHT_PACK BF16_BASE) when the stage carries S2K_FLAG_BF16,
+                         // its hi / mid / lo planes (SPLIT_BASE) with S2K_FLAG_SPLIT, else null
     const float* wtq;    // f32 quad copy of the packed weights ([KP/8][MP][8], WEIGHT_PACK Q4_BASE) when the stage carries S2K_FLAG_Q4, else null
     float* y;
     float* scratch;      // split-K partial tiles [splits][Y layout] (deep, short-N layers), or null
@@ -45,5 +46,7 @@ int launch_conv_dma(ConvP& p, hipStream_t st);
 int launch_conv_q4(ConvP& p, hipStream_t st);
 // conv_bf16.hip (bf16-mixed plans only: p.wtb set): same return convention
 int launch_conv_bf16(ConvP& p, hipStream_t st);
+// conv_bf16.hip, f32-split stages (S2K_FLAG_SPLIT, p.wtb = the split weight planes): S2K_OK = launched, < 0 = error (never declines)
+int launch_conv_split(ConvP& p, hipStream_t st);
 
 }  // namespace s2k

@@ -738,7 +738,11 @@ int launch_conv(const S2kOp& op, const Ctx& c) {
     p.stats = ref_ptr<double>(c, op.t[S2K_CONV_T_STATS]);
     p.res = ref_ptr<const float>(c, op.t[S2K_CONV_T_RES]);
     p.scratch = ref_ptr<float>(c, op.t[S2K_CONV_T_SCRATCH]);
-    p.wtb = (op.flags & S2K_FLAG_BF16) ? ref_ptr<const void>(c, op.t[S2K_CONV_T_WTB]) : nullptr;
+    const bool split = (op.flags & S2K_FLAG_SPLIT) != 0;
+    if (split && (op.flags & (S2K_FLAG_BF16 | S2K_FLAG_Q4 | S2K_FLAG_DMA | S2K_FLAG_RES_GELU_GRAD))) {
+        set_error("conv: S2K_FLAG_SPLIT excludes S2K_FLAG_BF16 / Q4 / DMA / RES_GELU_GRAD"); return S2K_EINVAL;
+    }
+    p.wtb = (op.flags & (S2K_FLAG_BF16 | S2K_FLAG_SPLIT)) ? ref_ptr<const void>(c, op.t[S2K_CONV_T_WTB]) : nullptr;
     p.wtq = (!(op.flags & S2K_FLAG_BF16) && (op.flags & S2K_FLAG_Q4)) ? ref_ptr<const float>(c, op.t[S2K_CONV_T_WTB]) : nullptr;
     p.force_dma = (op.flags & S2K_FLAG_DMA) ? 1 : 0;
     p.res_mul = (op.flags & S2K_FLAG_RES_GELU_GRAD) ? S2K_PRO_GELU : 0;
@@ -794,6 +798,7 @@ int launch_conv(const S2kOp& op, const Ctx& c) {
     p.Ntot = (int)ntot;
 
     hipStream_t st = c.stream;
+    if (split) return launch_conv_split(p, st);     // f32-split plan: the split kernels or an error, never another kernel
     if (p.wtb) {   // bf16-mixed plan: the shapes of conv_bf16.hip round their MFMA operands to bf16; 1 = not one of its shapes
         const int rc = launch_conv_bf16(p, st);
         if (rc != 1) return rc;

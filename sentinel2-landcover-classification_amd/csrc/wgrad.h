@@ -28,6 +28,8 @@ int launch_wgrad_pc(WgradP& p, int mode, hipStream_t st);
 int launch_wgrad_q4(WgradP& p, int mode, hipStream_t st);
 // wgrad_bf16.hip (stages carrying S2K_FLAG_BF16 in bf16-mixed plans): same return convention
 int launch_wgrad_bf16(WgradP& p, int mode, hipStream_t st);
+// wgrad_bf16.hip, f32-split stages (S2K_FLAG_SPLIT): S2K_OK = launched, < 0 = error (never declines)
+int launch_wgrad_split(WgradP& p, int mode, hipStream_t st);
 
 // bijective remap: consecutive logical tiles land on the same XCD (hardware deals blocks round-robin over the 8 XCDs;
 // which XCD is irrelevant, only that ids congruent mod 8 share one)

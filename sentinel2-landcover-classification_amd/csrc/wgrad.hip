@@ -479,6 +479,10 @@ int launch_wgrad(const S2kOp& op, const Ctx& c) {
     p.exp = wg_exp;
     hipStream_t st = c.stream;
     const int64_t npix = (int64_t)p.B * p.HWp;
+    if (op.flags & S2K_FLAG_SPLIT) {  // f32-split plan: the split kernels or an error, never another kernel
+        if (op.flags & S2K_FLAG_BF16) { set_error("wgrad: S2K_FLAG_SPLIT excludes S2K_FLAG_BF16"); return S2K_EINVAL; }
+        return launch_wgrad_split(p, mode, st);
+    }
     if (op.flags & S2K_FLAG_BF16) {   // bf16-mixed plan: the shapes of wgrad_bf16.hip round their MFMA operands to bf16; 1 = not one of them
         const int rc = launch_wgrad_bf16(p, mode, st);
         if (rc != 1) return rc;

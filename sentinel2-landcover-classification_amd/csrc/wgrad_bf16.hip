@@ -35,9 +35,10 @@ __device__ __forceinline__ uint32_t wpk(float lo, float hi) {
 }
 __device__ __forceinline__ uint32_t shr16(uint32_t hi, uint32_t lo) { return __builtin_amdgcn_alignbit(hi, lo, 16); }   // {hi, lo} >> 16
 
-// prologue of 8 consecutive pixels of one row -> one bf16 unit; `valid` = the pixels exist (zero padding / ragged tiles: the
-// reference pads ACTIVATED maps with zeros)
-__device__ __forceinline__ wu32x4 pro_unit(const f32x4& a, const f32x4& b, int pro, float sc, float sh, float gate, bool valid) {
+// prologue of 8 consecutive pixels of one row -> one bf16 unit per plane (SPLIT: hi / mid / lo, common.h split_bf16x2); `valid` =
+// the pixels exist (zero padding / ragged tiles: the reference pads ACTIVATED maps with zeros)
+template <bool SPLIT>
+__device__ __forceinline__ void pro_unit(wu32x4* w, const f32x4& a, const f32x4& b, int pro, float sc, float sh, float gate, bool valid) {
     float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
     if (pro != S2K_PRO_NONE) {
 #pragma unroll
@@ -45,9 +46,20 @@ __device__ __forceinline__ wu32x4 pro_unit(const f32x4& a, const f32x4& b, int p
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] *= gate;
-    wu32x4 w = {wpk(v[0], v[1]), wpk(v[2], v[3]), wpk(v[4], v[5]), wpk(v[6], v[7])};
-    if (!valid) w = wu32x4{0u, 0u, 0u, 0u};
-    return w;
+    if constexpr (SPLIT) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            uint32_t h, m, l;
+            split_bf16x2(v[2 * k], v[2 * k + 1], h, m, l);
+            w[0][k] = h; w[1][k] = m; w[2][k] = l;
+        }
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+            if (!valid) w[pl] = wu32x4{0u, 0u, 0u, 0u};
+    } else {
+        w[0] = wu32x4{wpk(v[0], v[1]), wpk(v[2], v[3]), wpk(v[4], v[5]), wpk(v[6], v[7])};
+        if (!valid) w[0] = wu32x4{0u, 0u, 0u, 0u};
+    }
 }
 
 // The four waves are arranged WVM (m) x WVC (c) x WVK (k): each computes WM x WN accumulator tiles of 32 x 32 per tap over the
@@ -57,9 +69,14 @@ __device__ __forceinline__ wu32x4 pro_unit(const f32x4& a, const f32x4& b, int p
 // 1x1: two workgroups per CU; 3x3 (144 accumulator registers per lane + the next tile's staging registers): one.
 // P16 (no prologue on P): P is stored as bf16 [B][M][HW] (a BN_BWD_APPLY with OUT_BF16 wrote it): a lane's 8 pixels are ONE
 // 16-byte load and ARE the LDS unit - the values the f32 path would round to.
-template <int MODE, int WVM, int WVC, int WM, int WN, int R, int XW, bool P16 = false>
+// SPLIT (the f32-SPLIT mode, S2K_FLAG_SPLIT): both operands as three bf16 planes hi / mid / lo, split once at staging time (each
+// plane in the layout above; the halo shifts are done per plane), six MFMAs per k-step and tap into the one accumulator, small terms
+// first: mid*mid, hi*lo, lo*hi, hi*mid, mid*hi, hi*hi (see conv_bf16.hip).
+template <int MODE, int WVM, int WVC, int WM, int WN, int R, int XW, bool P16 = false, bool SPLIT = false>
 __global__ void __launch_bounds__(256, MODE == WG_PIX ? 2 : 1) wgrad_bf16_kernel(const WgradP p) {
     constexpr bool PIX = MODE == WG_PIX;
+    static_assert(!(P16 && SPLIT), "split: f32 operands");
+    constexpr int NPL = SPLIT ? 3 : 1;                       // operand planes
 
     constexpr int NT = 256;
     constexpr int T = PIX ? 1 : 9;
@@ -77,9 +94,10 @@ __global__ void __launch_bounds__(256, MODE == WG_PIX ? 2 : 1) wgrad_bf16_kernel
     constexpr int POB = (NPO + 7) / 8, QOB = (NQO + 7) / 8;      // octet blocks (8 octets = one wave instruction's width)
     constexpr int NHI = PIX ? 0 : (BC * QR * 2 + NT - 1) / NT;   // halo-pixel items per thread
     static_assert(PIX || (XW % 8 == 0 && NPO % 2 == 0), "3x3 tile: whole octets, whole k-steps");
+    constexpr int Q_UNITS = QR * QXO * BC;
     extern __shared__ __attribute__((aligned(16))) wu32x4 smem_w[];
-    wu32x4* Ps = smem_w;
-    wu32x4* Qs = smem_w + P_UNITS;
+    wu32x4* Ps = smem_w;                                     // [NPL][P_UNITS]
+    wu32x4* Qs = smem_w + NPL * P_UNITS;                     // [NPL][Q_UNITS]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int mc = p.n_mtiles * p.n_ctiles;
@@ -218,7 +236,12 @@ __global__ void __launch_bounds__(256, MODE == WG_PIX ? 2 : 1) wgrad_bf16_kernel
 #pragma unroll
                 for (int j = 0; j < PRG; ++j) {
                     if constexpr (P16) Ps[oct * BM + (wave + 4 * j) * 8 + r8] = pok[ob] ? __builtin_bit_cast(wu32x4, pxa[ob][j]) : wu32x4{0u, 0u, 0u, 0u};
-                    else Ps[oct * BM + (wave + 4 * j) * 8 + r8] = pro_unit(pxa[ob][j], pxb[ob][j], p.prop, psc[j], psh[j], 1.0f, pok[ob]);
+                    else {
+                        wu32x4 w[NPL];
+                        pro_unit<SPLIT>(w, pxa[ob][j], pxb[ob][j], p.prop, psc[j], psh[j], 1.0f, pok[ob]);
+#pragma unroll
+                        for (int pl = 0; pl < NPL; ++pl) Ps[pl * P_UNITS + oct * BM + (wave + 4 * j) * 8 + r8] = w[pl];
+                    }
                 }
         }
 #pragma unroll
@@ -227,8 +250,12 @@ __global__ void __launch_bounds__(256, MODE == WG_PIX ? 2 : 1) wgrad_bf16_kernel
             if (oct < NQO) {
                 const int slot = PIX ? oct : (oct / XO) * QXO + 1 + (oct % XO);
 #pragma unroll
-                for (int j = 0; j < QRG; ++j)
-                    Qs[slot * BC + (wave + 4 * j) * 8 + r8] = pro_unit(qxa[ob][j], qxb[ob][j], p.proq, qsc[j], qsh[j], qgate[ob][j], qok[ob]);
+                for (int j = 0; j < QRG; ++j) {
+                    wu32x4 w[NPL];
+                    pro_unit<SPLIT>(w, qxa[ob][j], qxb[ob][j], p.proq, qsc[j], qsh[j], qgate[ob][j], qok[ob]);
+#pragma unroll
+                    for (int pl = 0; pl < NPL; ++pl) Qs[pl * Q_UNITS + slot * BC + (wave + 4 * j) * 8 + r8] = w[pl];
+                }
             }
         }
         if constexpr (!PIX) {
@@ -240,7 +267,12 @@ __global__ void __launch_bounds__(256, MODE == WG_PIX ? 2 : 1) wgrad_bf16_kernel
                     const int side = rest & 1, hr = rest >> 1;
                     const float x = hval[NHI > 0 ? i : 0];
                     // left halo pixel = element 7 of the unit left of octet 0; right halo pixel = element 0 of the unit after the last
-                    Qs[(hr * QXO + (side ? XO + 1 : 0)) * BC + c] = side ? wu32x4{wpk(x, 0.0f), 0u, 0u, 0u} : wu32x4{0u, 0u, 0u, wpk(0.0f, x)};
+                    uint32_t xs[3];
+                    if constexpr (SPLIT) split_bf16x2(x, 0.0f, xs[0], xs[1], xs[2]);
+                    else xs[0] = wpk(x, 0.0f);
+#pragma unroll
+                    for (int pl = 0; pl < NPL; ++pl)
+                        Qs[pl * Q_UNITS + (hr * QXO + (side ? XO + 1 : 0)) * BC + c] = side ? wu32x4{xs[pl], 0u, 0u, 0u} : wu32x4{0u, 0u, 0u, xs[pl] << 16};
                 }
             }
         }
@@ -257,16 +289,35 @@ __global__ void __launch_bounds__(256, MODE == WG_PIX ? 2 : 1) wgrad_bf16_kernel
         for (int s0 = 0; s0 < NPO / 2; s0 += WVK) {
             const int s = s0 + wk;                                      // this wave's k-step (16 pixels)
             const int o = 2 * s + lh;                                   // this lane half's pixel octet
-            wb16x8 a[WM];
+            wb16x8 a[NPL][WM];
 #pragma unroll
-            for (int rm = 0; rm < WM; ++rm) a[rm] = __builtin_bit_cast(wb16x8, Ps[o * BM + wm0 + rm * 32 + l31]);
+            for (int pl = 0; pl < NPL; ++pl)
+#pragma unroll
+                for (int rm = 0; rm < WM; ++rm) a[pl][rm] = __builtin_bit_cast(wb16x8, Ps[pl * P_UNITS + o * BM + wm0 + rm * 32 + l31]);
+            // acc += A x B: one MFMA, or (SPLIT, plane 0 = hi, 1 = mid, 2 = lo) the six significant cross products, small terms first
+            auto mma = [&](f32x16& c, const wb16x8* ap, const wb16x8* bp) {
+                if constexpr (SPLIT) {
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[1], bp[1], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0], bp[2], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[2], bp[0], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0], bp[1], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[1], bp[0], c, 0, 0, 0);
+                }
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[0], bp[0], c, 0, 0, 0);
+            };
             if constexpr (PIX) {
 #pragma unroll
                 for (int rn = 0; rn < WN; ++rn) {
-                    const wb16x8 b = __builtin_bit_cast(wb16x8, Qs[o * BC + wc0 + rn * 32 + l31]);
+                    wb16x8 b[NPL];
 #pragma unroll
-                    for (int rm = 0; rm < WM; ++rm)
-                        acc[0][rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rm], b, acc[0][rm][rn], 0, 0, 0);
+                    for (int pl = 0; pl < NPL; ++pl) b[pl] = __builtin_bit_cast(wb16x8, Qs[pl * Q_UNITS + o * BC + wc0 + rn * 32 + l31]);
+#pragma unroll
+                    for (int rm = 0; rm < WM; ++rm) {
+                        wb16x8 am[NPL];
+#pragma unroll
+                        for (int pl = 0; pl < NPL; ++pl) am[pl] = a[pl][rm];
+                        mma(acc[0][rm][rn], am, b);
+                    }
                 }
             } else {
                 const int r = o / XO, k = o % XO;
@@ -274,19 +325,26 @@ __global__ void __launch_bounds__(256, MODE == WG_PIX ? 2 : 1) wgrad_bf16_kernel
                 for (int rn = 0; rn < WN; ++rn)
 #pragma unroll
                     for (int dy = 0; dy < 3; ++dy) {
-                        const wu32x4* base = Qs + ((r + dy) * QXO + 1 + k) * BC + wc0 + rn * 32 + l31;
-                        const wu32x4 cur = base[0];
-                        const uint32_t pl = reinterpret_cast<const uint32_t*>(base - BC)[3];     // last dword of the unit to the left
-                        const uint32_t nf = reinterpret_cast<const uint32_t*>(base + BC)[0];     // first dword of the unit to the right
-                        const uint32_t s01 = shr16(cur[1], cur[0]), s12 = shr16(cur[2], cur[1]), s23 = shr16(cur[3], cur[2]);
-                        const wu32x4 left = {shr16(cur[0], pl), s01, s12, s23};                   // pixels x - 1 .. x + 6
-                        const wu32x4 right = {s01, s12, s23, shr16(nf, cur[3])};                  // pixels x + 1 .. x + 8
-                        const wb16x8 b0 = __builtin_bit_cast(wb16x8, left), b1 = __builtin_bit_cast(wb16x8, cur), b2 = __builtin_bit_cast(wb16x8, right);
+                        wb16x8 b0[NPL], b1[NPL], b2[NPL];
+#pragma unroll
+                        for (int pl = 0; pl < NPL; ++pl) {
+                            const wu32x4* base = Qs + pl * Q_UNITS + ((r + dy) * QXO + 1 + k) * BC + wc0 + rn * 32 + l31;
+                            const wu32x4 cur = base[0];
+                            const uint32_t lw = reinterpret_cast<const uint32_t*>(base - BC)[3];     // last dword of the unit to the left
+                            const uint32_t nf = reinterpret_cast<const uint32_t*>(base + BC)[0];     // first dword of the unit to the right
+                            const uint32_t s01 = shr16(cur[1], cur[0]), s12 = shr16(cur[2], cur[1]), s23 = shr16(cur[3], cur[2]);
+                            const wu32x4 left = {shr16(cur[0], lw), s01, s12, s23};                   // pixels x - 1 .. x + 6
+                            const wu32x4 right = {s01, s12, s23, shr16(nf, cur[3])};                  // pixels x + 1 .. x + 8
+                            b0[pl] = __builtin_bit_cast(wb16x8, left); b1[pl] = __builtin_bit_cast(wb16x8, cur); b2[pl] = __builtin_bit_cast(wb16x8, right);
+                        }
 #pragma unroll
                         for (int rm = 0; rm < WM; ++rm) {
-                            acc[dy * 3 + 0][rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rm], b0, acc[dy * 3 + 0][rm][rn], 0, 0, 0);
-                            acc[dy * 3 + 1][rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rm], b1, acc[dy * 3 + 1][rm][rn], 0, 0, 0);
-                            acc[dy * 3 + 2][rm][rn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rm], b2, acc[dy * 3 + 2][rm][rn], 0, 0, 0);
+                            wb16x8 am[NPL];
+#pragma unroll
+                            for (int pl = 0; pl < NPL; ++pl) am[pl] = a[pl][rm];
+                            mma(acc[dy * 3 + 0][rm][rn], am, b0);
+                            mma(acc[dy * 3 + 1][rm][rn], am, b1);
+                            mma(acc[dy * 3 + 2][rm][rn], am, b2);
                         }
                     }
             }
@@ -301,13 +359,13 @@ __global__ void __launch_bounds__(256, MODE == WG_PIX ? 2 : 1) wgrad_bf16_kernel
 }
 
 // -------------------------------------------------------------------------------------------------
-template <int MODE, int WVM, int WVC, int WM, int WN, int R, int XW, bool P16 = false>
+template <int MODE, int WVM, int WVC, int WM, int WN, int R, int XW, bool P16 = false, bool SPLIT = false>
 static int launch_wb16(WgradP& p, hipStream_t st) {
     constexpr bool PIX = MODE == WG_PIX;
     constexpr int BM = WVM * WM * 32, BC = WVC * WN * 32;
     constexpr int NPJ = PIX ? XW : R * XW;
     constexpr int XO = XW / 8, NPO = PIX ? XO : R * XO, QR = PIX ? 1 : R + 2, QXO = PIX ? XO : XO + 2;
-    constexpr size_t lds = (size_t)(NPO * BM + QR * QXO * BC) * 16;
+    constexpr size_t lds = (size_t)(NPO * BM + QR * QXO * BC) * 16 * (SPLIT ? 3 : 1);
     static_assert(lds <= 160 * 1024, "LDS image");
     p.n_mtiles = cdiv(p.M, BM);
     p.n_ctiles = cdiv(p.C, BC);
@@ -324,9 +382,12 @@ static int launch_wb16(WgradP& p, hipStream_t st) {
     {   // 32-bit buffer offsets: one image below 2 GiB when tiles are image-local, else the whole tensor
         const int64_t span = (!PIX || (p.HWp % NPJ) == 0) ? 1 : std::min<int64_t>(p.B, (NPJ - 2) / p.HWp + 2);   // images one pixel tile touches
         const int64_t need = std::max((int64_t)p.M * p.HWp, (int64_t)p.C * p.HWq) * 4 * span;
-        if (need >= 0x7ffffff0ll) return 1;
+        if (need >= 0x7ffffff0ll) {
+            if (SPLIT) { set_error("wgrad: f32-split stage: the images one tile touches exceed 2 GiB (%lld B)", (long long)need); return S2K_EINVAL; }
+            return 1;
+        }
     }
-    auto kern = wgrad_bf16_kernel<MODE, WVM, WVC, WM, WN, R, XW, P16>;
+    auto kern = wgrad_bf16_kernel<MODE, WVM, WVC, WM, WN, R, XW, P16, SPLIT>;
     static PerDeviceOnce attr_once;
     attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     // Pixel splits.  Every split ends in an atomic combine of its accumulator tiles, and float atomics run at ~1.3 TB/s chip-wide
@@ -342,7 +403,7 @@ static int launch_wb16(WgradP& p, hipStream_t st) {
     p.tiles_per_split = cdiv(p.ntiles, splits);
     splits = cdiv(p.ntiles, p.tiles_per_split);
     hipLaunchKernelGGL(kern, dim3(mc * splits), dim3(256), lds, st, p);
-    g_s2k_variant = 2;
+    g_s2k_variant = SPLIT ? 5 : 2;
     return S2K_OK;
 }
 
@@ -388,6 +449,39 @@ int launch_wgrad_bf16(WgradP& p, int mode, hipStream_t st) {
     if (p.WO == 16) return WB16_3X3(2, 2, 1, 1, 8, 16);
 #undef WB16_3X3
     return 1;
+}
+
+// f32-split (S2K_FLAG_SPLIT): S2K_OK = launched, < 0 = error - a split stage never falls back (plan/split.py lists these shapes).
+// Three operand planes: the 1x1 tiles are those of bf16-mixed (image 96 KiB: one workgroup per CU); the 3x3 pixel tiles are halved
+// (2 x 32 / 2 x 64 / 4 x 16 pixels, image 96 - 144 KiB, one workgroup per CU), the 224-pixel-input widths (56 / 112 / 224) not taken.
+int launch_wgrad_split(WgradP& p, int mode, hipStream_t st) {
+    auto no = [] { set_error("wgrad: f32-split stage with a shape the split kernels do not take (plan/split.py)"); return S2K_EINVAL; };
+    if (p.p_bf16) { set_error("wgrad: f32-split stages read f32 operands (P_BF16 set)"); return S2K_EINVAL; }
+    if (mode != S2K_MODE_CONV || p.S != 1 || p.H != p.HO || p.W != p.WO || p.gatep) return no();
+    auto pro_ok = [](int pro) { return pro == S2K_PRO_NONE || pro == S2K_PRO_RELU || pro == S2K_PRO_SILU || pro == S2K_PRO_AFFINE || pro == S2K_PRO_GELU; };
+    if (!pro_ok(p.prop) || !pro_ok(p.proq)) return no();
+    auto edge = [](int n) { return n <= 32 ? 32 : ((n > 64 && (double)cdiv(n, 128) * 128 / n <= 1.12) ? 128 : 64); };
+    const int em = edge(p.M), ec = edge(p.C);
+    if (p.T == 1) {
+        if ((p.HWp & 7) || (int64_t)p.B * p.HWp < 512) return no();
+        if (em == 32 && ec == 32) return launch_wb16<WG_PIX, 1, 1, 1, 1, 1, 256, false, true>(p, st);
+        if (em == 32) return launch_wb16<WG_PIX, 1, 2, 1, 1, 1, 128, false, true>(p, st);
+        if (ec == 32) return launch_wb16<WG_PIX, 2, 1, 1, 1, 1, 128, false, true>(p, st);
+        if (em == 128 && ec == 128) return launch_wb16<WG_PIX, 2, 2, 2, 2, 1, 64, false, true>(p, st);
+        if (em == 128) return launch_wb16<WG_PIX, 2, 2, 2, 1, 1, 64, false, true>(p, st);
+        if (ec == 128) return launch_wb16<WG_PIX, 2, 2, 1, 2, 1, 64, false, true>(p, st);
+        return launch_wb16<WG_PIX, 2, 2, 1, 1, 1, 64, false, true>(p, st);
+    }
+    if (p.T != 9 || p.KH != 3 || p.KW != 3 || p.PT != 1 || p.PL != 1 || p.gateq || p.prop != S2K_PRO_NONE) return no();
+    if (p.WO % 64 == 0) {
+        if (em == 32 && ec == 32) return launch_wb16<WG_SPATIAL, 1, 1, 1, 1, 4, 64, false, true>(p, st);
+        if (em == 32) return launch_wb16<WG_SPATIAL, 1, 2, 1, 1, 2, 64, false, true>(p, st);
+        if (ec == 32) return launch_wb16<WG_SPATIAL, 2, 1, 1, 1, 2, 64, false, true>(p, st);
+        return launch_wb16<WG_SPATIAL, 2, 2, 1, 1, 2, 32, false, true>(p, st);
+    }
+    if (p.WO == 32) return launch_wb16<WG_SPATIAL, 2, 2, 1, 1, 2, 32, false, true>(p, st);
+    if (p.WO == 16) return launch_wb16<WG_SPATIAL, 2, 2, 1, 1, 4, 16, false, true>(p, st);
+    return no();
 }
 
 }  // namespace s2k

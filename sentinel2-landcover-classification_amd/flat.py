@@ -77,13 +77,16 @@ class FlatParamsMixin:
         """"f32" (default: exact-f32 MFMA everywhere, the parity path) or "bf16-mixed": dense convs / Linears and their weight
         gradients may round their MFMA operands to bf16 (f32 accumulation, f32 BatchNorm / LayerNorm / attention / loss / master
         weights / Adam) - the arithmetic class of the reference's own default `precision="bf16"` (configs/segmentation.py:146,153,
-        prithvi_mae_finetune.py), reported separately from the f32 results and never the default."""
+        prithvi_mae_finetune.py), reported separately from the f32 results and never the default.
+        "f32-split": f32-accurate on the bf16 matrix cores - the dense convs / Linears and weight gradients that plan/split.py routes
+        split each f32 MFMA operand into three bf16 terms (hi + mid + lo) and accumulate the six significant cross products in f32;
+        everything else is the "f32" plan.  The method-path and encoder-only planners plan exact f32 in this mode (as for bf16-mixed)."""
         return getattr(self, "_precision", "f32")
 
     @precision.setter
     def precision(self, value: str) -> None:
-        if value not in ("f32", "bf16-mixed"):
-            raise ValueError(f"precision must be 'f32' or 'bf16-mixed', got {value!r}")
+        if value not in ("f32", "bf16-mixed", "f32-split"):
+            raise ValueError(f"precision must be 'f32', 'bf16-mixed' or 'f32-split', got {value!r}")
         if value != self.precision:
             self._precision = value
             self._engines.clear()

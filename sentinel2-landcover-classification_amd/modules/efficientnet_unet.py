@@ -289,7 +289,7 @@ class EfficientnetUnet(FlatParamsMixin, nn.Module):
     def _make_plan(self, B: int, H: int, W: int, training: bool, want_bwd: bool | None = None, want_dx: bool = False):
         return plan_unet(self.spec, B, H, W, training, self._layout, defer_wgrads=getattr(self, "_defer_wgrads", None),
                          want_bwd=want_bwd, bucket_floats=getattr(self, "_bucket_floats", 8 << 20), want_dx=want_dx,
-                         bf16=self.precision == "bf16-mixed")
+                         bf16=self.precision == "bf16-mixed", split=self.precision == "f32-split")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.dim() != 4 or x.shape[1] != self.config.in_channels:

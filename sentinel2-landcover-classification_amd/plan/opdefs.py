@@ -45,6 +45,10 @@ FLAG_Q4 = 16        # CONV (f32 plans): WTB holds the f32 "quad" copy of WT that
 FLAG_RES_GELU_GRAD = 32   # CONV with RES: Y = (conv + bias) * gelu'(RES) instead of + RES - the backward of "GELU then Linear" in one stage
                     # (fc2's data gradient times gelu'(fc1 output): timm Mlp, prithvi.py:162-183), f32 plans; the producer / consumer and
                     # generic kernels implement it, the other CONV kernels decline such a stage
+FLAG_SPLIT = 64     # CONV / WGRAD, f32-SPLIT plans only: the stage computes its contraction with each f32 MFMA operand split into three
+                    # bf16 terms (hi + mid + lo, six bf16 MFMAs per k-step into the f32 accumulator: csrc/conv_bf16.hip, wgrad_bf16.hip
+                    # with SPLIT) - f32-accurate.  CONV then reads the hi / mid / lo weight copy WTB that WEIGHT_PACK wrote (SPLIT_BASE).
+                    # Only the shapes of plan/split.py carry it; a flagged stage runs on the split kernels or fails (S2K_EINVAL).
 FLAG_DMA = 8        # CONV: take the LDS-DMA ring kernel (csrc/conv_dma.hip) for every shape it supports, not only where its launcher's
                     # measured routing rule sends a stage (tests cover all of its tiles this way; plans leave the choice to the launcher)
 
@@ -68,7 +72,9 @@ OPS: dict[str, tuple[list[str], list[str], list[str], list[str]]] = {
     # fragment order of the bf16 MFMA kernels, [KP/8][T][MP][8]: element ((kc/8 * T + tap) * MP + m) * 8 + kc % 8
     # Q4_BASE > 0 (f32 plans): additionally DST_bytes[Q4_BASE + 4*dst_off ...] receives every 1x1 entry (T = 1) in the quad layout
     # [KP/8][MP][8]: element ((kc >> 3) * MP + m) * 8 + (kc & 1) * 4 + ((kc >> 1) & 3)   (csrc/conv_q4.hip; FLAG_Q4 stages read it as WTB)
-    "WEIGHT_PACK": (["TABLE", "SRC", "DST"], ["TOTAL", "BF16_BASE", "Q4_BASE"], ["N_ENTRIES"], []),
+    # SPLIT_BASE > 0 (f32-split plans): additionally DST_bytes[SPLIT_BASE + 6*dst_off ...] receives every entry as three bf16 planes
+    # hi / mid / lo (x = hi + mid + lo, see FLAG_SPLIT), each an entry-sized copy in the BF16_BASE fragment order, one after the other
+    "WEIGHT_PACK": (["TABLE", "SRC", "DST"], ["TOTAL", "BF16_BASE", "Q4_BASE", "SPLIT_BASE"], ["N_ENTRIES"], []),
     # Implicit-GEMM convolution on f32 MFMA (fwd conv / convT fwd / conv dgrad / convT dgrad):
     #   Y[b][m][yo][xo] (+)= BIAS[m] + sum_{c,ky,kx} Wv[m][c][ky][kx] * Xpro[b][c][yo*S+ky-PT][xo*S+kx-PL]
     # with Wv[m][c][tap] = WT[m*W_SM + c*W_SK + (FLIP ? T-1-tap : tap)*W_ST] (the HIP kernel requires the
@@ -81,7 +87,7 @@ OPS: dict[str, tuple[list[str], list[str], list[str], list[str]]] = {
     # A Linear over feature-major tokens [B][C][L] is this stage with H = 1, W = L.
     # SCRATCH (optional, >= 8 * B*YC*HO*WO floats): lets the kernel cut a long reduction over few output tiles into
     # split-K partials that a tail kernel adds in a fixed order (deep 8x8 / 16x16 layers: 160 tiles cannot fill 256 CUs).
-    # WTB (with FLAG_BF16): the bf16 copy of WT written by WEIGHT_PACK (BF16_BASE)
+    # WTB (with FLAG_BF16): the bf16 copy of WT written by WEIGHT_PACK (BF16_BASE); with FLAG_SPLIT: its hi / mid / lo planes (SPLIT_BASE)
     # X1_BF16 (bf16-mixed plans, 1x1 stages with FLAG_BF16, PRO1 = NONE, C2 = 0): X1 is stored as bf16 [B][C1][HW] - the output of a
     # BN_BWD_APPLY with OUT_BF16.  The stage would round exactly these values to bf16 when it builds its MFMA operand, so results are
     # bit-identical to reading the f32 tensor; the apply pass writes, and both consumers read, half the bytes.

@@ -888,6 +888,8 @@ def finish_plan(p: "_P", layout: ParamLayout, training: bool, bucket_floats: int
     attach_splitk_scratch()
     if getattr(p, "bf16", False):
         mark_bf16(p, bwd)
+    if getattr(p, "split", False):
+        mark_split(p, bwd)
     return segments, bwd
 
 
@@ -988,6 +990,37 @@ def mark_bf16(p: "_P", bwd) -> None:
             elif kind == "WGRAD" and B16.wgrad_ok(f):
                 f["_flags"] = f.get("_flags", 0) | D.FLAG_BF16
     p.wpack.top = base + (base + 1) // 2 + 256
+
+
+def mark_split(p: "_P", bwd) -> None:
+    """f32-SPLIT plan: the f32 plan as it stands, plus FLAG_SPLIT on the dense convs / Linears / data gradients / weight gradients
+    that plan/split.py routes to the split kernels (each f32 MFMA operand as three bf16 terms, six bf16 MFMAs per k-step: f32-accurate).
+    WEIGHT_PACK writes the hi / mid / lo planes of every packed weight into a mirror region behind the packs (SPLIT_BASE) and a flagged
+    CONV reads its entry there as WTB.  Stages the f32 plan already sends to a dedicated kernel (FLAG_Q4, FLAG_RES_GELU_GRAD,
+    FLAG_DMA) keep it; everything not flagged computes exactly as in the "f32" plan.  The emulator treats the flag as exact f32."""
+    from . import split as SP
+
+    base = (p.wpack.mark() + 255) // 256 * 256
+    keep = D.FLAG_Q4 | D.FLAG_RES_GELU_GRAD | D.FLAG_DMA | D.FLAG_BF16
+    packs, split_convs = [], 0
+    for prog in (p.fwd, bwd):
+        if prog is None:
+            continue
+        for kind, f in prog.ops:
+            if kind == "WEIGHT_PACK":
+                packs.append(f)
+            elif kind == "CONV" and isinstance(f.get("WT"), TRef) and f["WT"].base == D.BASE["WPACK"] and not (f.get("_flags", 0) & keep) \
+                    and f["WT"].shape[0] == -(-(f["C1"] + f["C2"]) // 64) * 64 * f["KH"] * f["KW"] and SP.routed(kind, f):
+                f["_flags"] = f.get("_flags", 0) | D.FLAG_SPLIT
+                f["WTB"] = TRef(D.BASE["WPACK"], base + 3 * (f["WT"].off // 2), f["WT"].shape, "i16", "split:" + f["WT"].name)
+                split_convs += 1
+            elif kind == "WGRAD" and not (f.get("_flags", 0) & D.FLAG_BF16) and SP.routed(kind, f):
+                f["_flags"] = f.get("_flags", 0) | D.FLAG_SPLIT
+    if not split_convs:          # (the MAE plans with the measured routing: no weight copy to write)
+        return
+    for f in packs:
+        f["SPLIT_BASE"] = base
+    p.wpack.top = base + 3 * ((base + 1) // 2) + 256
 
 
 def fold_bn_finalize(prog: Program) -> int:
@@ -1094,16 +1127,19 @@ def build_encoder_layout(spec: UnetSpec) -> ParamLayout:
 
 def plan_unet(spec: UnetSpec, B: int, H: int, W: int, training: bool, layout: ParamLayout | None = None,
               bucket_floats: int = 8 << 20, defer_wgrads: bool | None = None, want_bwd: bool | None = None,
-              want_dx: bool = False, bf16: bool = False) -> UnetPlan:
+              want_dx: bool = False, bf16: bool = False, split: bool = False) -> UnetPlan:
     """defer_wgrads: None = the S2K_DEFER_WGRAD default (on); False keeps the decoder's weight gradients where the tape emits
     them, so that gradient buckets become final progressively (what the data-parallel reducer wants, see ddp.py).
-    bf16: the bf16-mixed plan (mark_bf16)."""
+    bf16: the bf16-mixed plan (mark_bf16).  split: the f32-split plan (mark_split)."""
+    if bf16 and split:
+        raise ValueError("bf16 and split are two different precision modes")
     if H % 32 or W % 32:
         raise ValueError(f"EfficientnetUnet needs H, W multiples of 32, got {H}x{W}")
     layout = layout or build_layout(spec)
     p = _P(spec, layout, B, H, W, training, want_bwd)
     p.defer_wgrads = defer_wgrads
     p.bf16 = bool(bf16)
+    p.split = bool(split)
     eps, mom = spec.bn_eps, spec.bn_momentum
     # want_dx: the caller's input requires a gradient (torch semantics: x.requires_grad) — it lands in the DX base
     x_in = Act(TRef(D.BASE["X"], 0, (B, spec.in_channels, H, W), "f32", "x"), spec.in_channels, H, W,

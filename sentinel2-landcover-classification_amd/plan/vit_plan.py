@@ -26,6 +26,7 @@ import os
 from dataclasses import dataclass, field
 
 from . import opdefs as D
+from . import split as SP
 from .program import Program, TRef
 from .unet_plan import Act, ParamLayout, _P, _conv_dgrad_wgrad, _numel, conv_bn, conv_transpose, finish_plan
 
@@ -401,19 +402,24 @@ def _out(outs: dict, cursor: list, name: str, shape: tuple, dtype: str = "f32") 
 
 
 def plan_mae(s: MaeSpec, B: int, mask_ratio: float, training: bool, layout: ParamLayout | None = None,
-             bucket_floats: int = 8 << 20, want_dx: bool = False, bf16: bool = False) -> VitPlan:
+             bucket_floats: int = 8 << 20, want_dx: bool = False, bf16: bool = False, split: bool = False) -> VitPlan:
     """MaskedAutoencoderViT.forward(imgs, mask_ratio) -> (loss, pred, mask) (+ latent, ids_restore for forward_encoder).
     bf16: the bf16-mixed plan (unet_plan.mark_bf16: Linears and their weight gradients on bf16 MFMA operands; attention,
-    LayerNorm, GELU, loss and the optimiser stay f32); token rows are padded to 8 floats instead of 4."""
-    with _row_align(8 if bf16 else 4):
-        return _plan_mae(s, B, mask_ratio, training, layout, bucket_floats, want_dx, bf16)
+    LayerNorm, GELU, loss and the optimiser stay f32); token rows are padded to 8 floats instead of 4.
+    split: the f32-split plan (unet_plan.mark_split: the Linears and weight gradients plan/split.py routes compute on split bf16
+    operands, f32-accurate); token rows padded to 8 floats only where a routed split kernel needs pixel octets (split.wants_pixel_octets):
+    with the measured routing the Linears stay f32 and the plan keeps the f32 plan's rows."""
+    with _row_align(8 if bf16 or (split and SP.wants_pixel_octets()) else 4):
+        return _plan_mae(s, B, mask_ratio, training, layout, bucket_floats, want_dx, bf16, split)
 
 
-def _plan_mae(s: MaeSpec, B: int, mask_ratio: float, training: bool, layout, bucket_floats: int, want_dx: bool, bf16: bool) -> VitPlan:
+def _plan_mae(s: MaeSpec, B: int, mask_ratio: float, training: bool, layout, bucket_floats: int, want_dx: bool, bf16: bool,
+              split: bool = False) -> VitPlan:
     assert s.decoder
     layout = layout or mae_layout(s)
     p = _P(s, layout, B, s.img_size, s.img_size, training)
     p.bf16 = bool(bf16)
+    p.split = bool(split)
     v = _V(p, lambda name: True)
     Lp, Dm, Dd, PD = s.num_patches, s.embed_dim, s.decoder_embed_dim, s.patch_dim
     keep = int(Lp * (1 - mask_ratio))
@@ -497,13 +503,14 @@ def _plan_mae(s: MaeSpec, B: int, mask_ratio: float, training: bool, layout, buc
 
 
 def plan_seg(s: SegSpec, B: int, training: bool, layout: ParamLayout | None = None, bucket_floats: int = 8 << 20,
-             want_bwd: bool | None = None, want_dx: bool = False, bf16: bool = False) -> VitPlan:
-    """PrithviSegmentationNet.forward (prithvi_segmentation.py:156-162).  bf16: the bf16-mixed plan (see plan_mae)."""
-    with _row_align(8 if bf16 else 4):
-        return _plan_seg(s, B, training, layout, bucket_floats, want_bwd, want_dx, bf16)
+             want_bwd: bool | None = None, want_dx: bool = False, bf16: bool = False, split: bool = False) -> VitPlan:
+    """PrithviSegmentationNet.forward (prithvi_segmentation.py:156-162).  bf16 / split: the bf16-mixed / f32-split plan (see plan_mae)."""
+    with _row_align(8 if bf16 or (split and SP.wants_pixel_octets()) else 4):
+        return _plan_seg(s, B, training, layout, bucket_floats, want_bwd, want_dx, bf16, split)
 
 
-def _plan_seg(s: SegSpec, B: int, training: bool, layout, bucket_floats: int, want_bwd, want_dx: bool, bf16: bool) -> VitPlan:
+def _plan_seg(s: SegSpec, B: int, training: bool, layout, bucket_floats: int, want_bwd, want_dx: bool, bf16: bool,
+              split: bool = False) -> VitPlan:
     m = s.mae
     assert not m.decoder
     if m.img_size // m.patch_size * 16 != m.img_size:
@@ -511,6 +518,7 @@ def _plan_seg(s: SegSpec, B: int, training: bool, layout, bucket_floats: int, wa
     layout = layout or seg_layout(s)
     p = _P(s, layout, B, m.img_size, m.img_size, training, want_bwd)
     p.bf16 = bool(bf16)
+    p.split = bool(split)
     frozen = s.frozen_backbone
     v = _V(p, lambda name: not (frozen and name.startswith("backbone.")))
     Lp, Dm, E = m.num_patches, m.embed_dim, s.embed

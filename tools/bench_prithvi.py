@@ -26,7 +26,7 @@ def main():
     ap.add_argument("--unfrozen", action="store_true")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--ops", action="store_true", help="with --profile: per-shape table of the MFMA stages")
-    ap.add_argument("--precision", default="f32", choices=["f32", "bf16-mixed"])
+    ap.add_argument("--precision", default="f32", choices=["f32", "bf16-mixed", "f32-split"])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(42)

@@ -7,12 +7,17 @@ root=$(pwd)
 out=$root/gpurun_out/traffic_$tag
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
+# every profiled process under its own time limit; the first failure ends the run (nothing more is started on the GPU)
+pmc() {   # log counter dir cmd...
+  local log=$1 c=$2 d=$3; shift 3
+  timeout -k 10 900 rocprofv3 --pmc $c -d $d -o p --output-format csv -- "$@" > $log 2>&1 || { tail -5 $log; exit 1; }
+}
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $ctr -d $out/$ctr -o p --output-format csv -- python3 $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile > $out/$ctr.log 2>&1 || tail -5 $out/$ctr.log
+  pmc $out/$ctr.log $ctr $out/$ctr python3 $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile
   # calibration on known byte counts: a float4 stream (torch copy) and the dword-per-lane conv / depthwise kernels
-  rocprofv3 --pmc $ctr -d $out/cal_$ctr -o p --output-format csv -- python3 $root/tools/bench_op.py copy --C 144 --H 128 --iters 2 > $out/cal_$ctr.log 2>&1
-  rocprofv3 --pmc $ctr -d $out/cal2_$ctr -o p --output-format csv -- python3 $root/tools/bench_op.py dwfwd --C 240 --H 64 --S 1 --pro 0 --nostats --iters 2 > $out/cal2_$ctr.log 2>&1
-  rocprofv3 --pmc $ctr -d $out/cal3_$ctr -o p --output-format csv -- python3 $root/tools/bench_op.py conv3 --M 128 --C 128 --H 64 --iters 2 > $out/cal3_$ctr.log 2>&1
+  pmc $out/cal_$ctr.log $ctr $out/cal_$ctr python3 $root/tools/bench_op.py copy --C 144 --H 128 --iters 2
+  pmc $out/cal2_$ctr.log $ctr $out/cal2_$ctr python3 $root/tools/bench_op.py dwfwd --C 240 --H 64 --S 1 --pro 0 --nostats --iters 2
+  pmc $out/cal3_$ctr.log $ctr $out/cal3_$ctr python3 $root/tools/bench_op.py conv3 --M 128 --C 128 --H 64 --iters 2
 done
 python3 - <<PY
 import csv, glob, collections, json
