@@ -84,6 +84,9 @@ int s2k_program_profile_ops(const S2kOp* ops, int begin, int end, void* const* b
  * bf16 MFMA kernels (conv_bf16_kernel / wgrad_bf16_kernel; S2K_FLAG_BF16 stages), 3 for the LDS-DMA ring kernel
  * (conv_dma_kernel), 4 for the quad-read kernels (conv_q4_kernel: S2K_FLAG_Q4 stages; wgrad_q4_kernel: picked by the launcher),
  * 5 for the f32-split kernels (conv_bf16_kernel / wgrad_bf16_kernel with SPLIT: S2K_FLAG_SPLIT stages, which run nowhere else).
+ * Depthwise stages (DWCONV_FWD / _DGRAD / _WGRAD): 0 for the band kernels (dwconv_fwd_kernel, dwconv_dgrad_s1_kernel,
+ * dwconv_dgrad_s2_kernel, dwconv_wgrad_kernel), 6 for the wave-per-channel plane kernels (dwconv_{fwd,dgrad,wgrad}_plane_kernel,
+ * dwconv_{fwd,dgrad}_plane_s2_kernel), 7 for dwconv_wgrad_kernel walking images inside the workgroup (its image loop).
  * bench.py uses it to attribute time and algorithmic FLOPs to the kernel names a rocprofv3 trace shows. */
 int s2k_program_profile_variants(const S2kOp* ops, int begin, int end, void* const* bases, int n_bases, void* stream,
                                  float* ms_per_op, int* variant_per_op);

@@ -127,7 +127,9 @@ def profile_ops(packed: np.ndarray, bases: Bases, stream: int) -> np.ndarray:
 
 
 def profile_variants(packed: np.ndarray, bases: Bases, stream: int):
-    """(ms per stage, variant per stage): variant 1 = the producer/consumer kernel was launched (include/s2k.h)."""
+    """(ms per stage, variant per stage): the kernel family each stage's launcher picked (include/s2k.h,
+    s2k_program_profile_variants): 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads, 5 f32-split;
+    depthwise stages: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop."""
     ms = np.zeros(len(packed), dtype=np.float32)
     var = np.zeros(len(packed), dtype=np.int32)
     with _guard(bases):

@@ -1394,6 +1394,7 @@ int launch_dwconv_fwd(const S2kOp& op, const Ctx& c) {
             else DW_PLANE(5, 64, 16);
         }
 #undef DW_PLANE
+        g_s2k_variant = 6;
         return S2K_OK;
     }
     static const int s2_on = tune_int("S2K_DW_PLANE_S2", 1);
@@ -1418,6 +1419,7 @@ int launch_dwconv_fwd(const S2kOp& op, const Ctx& c) {
             if (p.WO == 8) DW_S2(5, 8, 8); else if (p.WO == 16) DW_S2(5, 16, 16); else if (p.WO == 32) DW_S2(5, 32, 8); else DW_S2(5, 64, 4);
         }
 #undef DW_S2
+        g_s2k_variant = 6;
         return S2K_OK;
     }
     // tile columns: source column cc - 4; the widest window ends at 4 - PL + (4*XG - 1)*S + K - 1
@@ -1475,6 +1477,7 @@ int launch_dwconv_wgrad(const S2kOp& op, const Ctx& c) {
             else DW_WGP(5, 64, 16);
         }
 #undef DW_WGP
+        g_s2k_variant = 6;
         return S2K_OK;
     }
     const int lw = 4 - p.PL + (cdiv(p.WO, 4) * 4 - 1) * p.S + p.K;
@@ -1496,6 +1499,7 @@ int launch_dwconv_wgrad(const S2kOp& op, const Ctx& c) {
             bsplits = cdiv(p.B, p.bloop);
             const bool silu_b = p.pro == S2K_PRO_SILU;
             const dim3 grid((unsigned)(p.cgroups * bsplits));
+            g_s2k_variant = 7;
 #define DW_WGB(KK, SS, PP) do { if (silu_b) hipLaunchKernelGGL((dwconv_wgrad_kernel<KK, SS, PP, S2K_PRO_SILU>), grid, dim3(NTHREADS), lds, c.stream, p); \
                                 else hipLaunchKernelGGL((dwconv_wgrad_kernel<KK, SS, PP, S2K_PRO_NONE>), grid, dim3(NTHREADS), lds, c.stream, p); return S2K_OK; } while (0)
 #define DW_WGB_PL(KK, SS) do { if (p.PL == 0) DW_WGB(KK, SS, 0); else if (p.PL == 1) DW_WGB(KK, SS, 1); else DW_WGB(KK, SS, 2); } while (0)
@@ -1563,6 +1567,7 @@ int launch_dwconv_dgrad(const S2kOp& op, const Ctx& c) {
                 else DW_DGP(5, 64, 16);
             }
 #undef DW_DGP
+            g_s2k_variant = 6;
             return S2K_OK;
         }
         const int lw = 4 - pr + cdiv(p.W, 4) * 4 + p.K - 1;
@@ -1597,6 +1602,7 @@ int launch_dwconv_dgrad(const S2kOp& op, const Ctx& c) {
             if (p.WO == 8) DW_DG2(5, 8, 8); else if (p.WO == 16) DW_DG2(5, 16, 16); else if (p.WO == 32) DW_DG2(5, 32, 8); else DW_DG2(5, 64, 4);
         }
 #undef DW_DG2
+        g_s2k_variant = 6;
         return S2K_OK;
     }
     const size_t lds = tile_rows(p, p.H, p.W, irt_dgrad2, p.WO + 2, true, false);   // one zero column on either side

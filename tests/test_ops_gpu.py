@@ -72,12 +72,16 @@ class Case:
         fields["BF16_BASE"] = dst16.off - dst.off // 2
         return ("WEIGHT_PACK", fields), dst, MP, dst16
 
-    def run(self, kind, outputs, tol=1e-4, sum0=(), pre=(), want_variant=None, per_column=(), **fields):
+    def run(self, kind, outputs, tol=1e-4, sum0=(), pre=(), want_variant=None, per_column=(), ref64=False, **fields):
         """sum0: outputs compared after summing their leading (statistics-replica) dimension.
         pre: stage records to run first (e.g. WEIGHT_PACK).  want_variant: the kernel family the stage must have taken
-        (s2k_program_profile_variants, include/s2k.h: 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads).
+        (s2k_program_profile_variants, include/s2k.h: 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads,
+        5 f32-split; depthwise: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop).
         per_column: outputs whose every last-dim column must also meet `tol` against that column's own max |ref| (a wrong
-        column among larger ones - e.g. a ragged last channel tile - hides under the whole tensor's max)."""
+        column among larger ones - e.g. a ragged last channel tile - hides under the whole tensor's max).
+        ref64: the outputs must also meet `tol` against a float64 run of the oracle (every f32 tensor held as float64 at twice its
+        offset, as plan_harness.make_bases(wide=True) lays out a plan), so that an error the f32 oracle shares cannot hide.
+        Returns {output: (error against the f32 oracle, error against float64 or None)}."""
         from s2lc_amd import _lib
 
         prog = Program()
@@ -95,7 +99,16 @@ class Case:
             _, var = _lib.profile_variants(packed, _lib.Bases().set("WS", cpu.cuda()), torch.cuda.current_stream().cuda_stream)
             assert int(var[-1]) == want_variant, f"{kind}: kernel family {int(var[-1])}, expected {want_variant}"
         got = gpu.cpu()
+        wide = None
+        if ref64:       # (from the inputs as written: the f32 oracle below overwrites `cpu` in place)
+            wide = torch.zeros(2 * cpu.numel(), dtype=torch.uint8)
+            for name, (ref, data) in self.items.items():
+                wdt = {"f32": torch.float64, "bf16": torch.float32}.get(ref.dtype)
+                b = (data.to(wdt) if wdt is not None else data).contiguous().reshape(-1).view(torch.uint8)
+                wide[2 * ref.off:2 * ref.off + b.numel()] = b
+            ops_ref.run_program(packed, {WS: wide}, D, wide=True)
         ops_ref.run_program(packed, {WS: cpu}, D)
+        errs = {}
         for name in outputs:
             ref, _ = self.items[name]
             a = got[ref.off:ref.off + ref.nbytes].view(_DT[ref.dtype]).double()
@@ -107,12 +120,24 @@ class Case:
             denom = max(b.abs().max().item(), 1e-20)
             err = (a - b).abs().max().item() / denom
             assert err < tol, f"{kind}:{name}: rel err {err:.3e} (max |ref| {denom:.3e})"
+            err64 = None
+            if wide is not None:
+                wdt = {"f32": torch.float64, "bf16": torch.float32}.get(ref.dtype, _DT[ref.dtype])
+                t = wide[2 * ref.off:2 * ref.off + ref.numel * wdt.itemsize].view(wdt).double()
+                if name in sum0:
+                    t = t.view(ref.shape).sum(0)
+                assert torch.isfinite(t).all(), f"{kind}:{name}: float64 oracle produced non-finite values"
+                d64 = max(t.abs().max().item(), 1e-20)
+                err64 = (a.reshape(t.shape) - t).abs().max().item() / d64
+                assert err64 < tol, f"{kind}:{name}: rel err {err64:.3e} against float64 (max |ref| {d64:.3e})"
+            errs[name] = (err, err64)
             if name in per_column:
                 n = ref.shape[-1]
                 a, b = a.reshape(-1, n), b.reshape(-1, n)
                 cerr = (a - b).abs().amax(0) / b.abs().amax(0).clamp_min(1e-20)
                 col = int(cerr.argmax())
                 assert cerr[col] < tol, f"{kind}:{name}: column {col} of {n}: rel err {cerr[col]:.3e} (its max |ref| {b[:, col].abs().max():.3e})"
+        return errs
 
 
 def _shape_ids(table, n):
@@ -731,12 +756,17 @@ def test_wgrad_finalize():
 # ---------------------------------------------------------------------------------------------------
 # depthwise
 # ---------------------------------------------------------------------------------------------------
-DW_GEOS = [(2, 24, 16, 16, 3, 1), (2, 40, 16, 16, 5, 2), (3, 16, 7, 7, 5, 1), (2, 8, 40, 40, 3, 2), (1, 6, 15, 13, 5, 2),
-           (1, 4, 64, 64, 5, 1), (2, 100, 8, 8, 3, 1), (1, 3, 130, 70, 3, 1),
-           # small square planes at stride 1: one wave per channel walks a chunk of the batch (ragged chunks, 4 planes per pass at 8 x 8)
-           (33, 12, 16, 16, 5, 1), (37, 10, 8, 8, 5, 1), (9, 6, 8, 8, 3, 1), (5, 70, 16, 16, 3, 1), (5, 10, 32, 32, 5, 1), (3, 6, 32, 32, 3, 1),
-           (3, 6, 64, 64, 3, 1), (5, 9, 64, 64, 5, 1), (2, 5, 128, 128, 3, 1),      # row bands of 16 / 8 rows with halo rows from the neighbouring bands
-           (3, 6, 128, 128, 3, 2), (5, 7, 64, 64, 5, 2), (9, 5, 32, 32, 3, 2), (4, 6, 32, 32, 5, 2), (6, 5, 16, 16, 3, 2)]   # stride 2 on even planes
+DW_GEOS = [   # (B, C, H, W, K, S, kernel family of (forward, data gradient, weight gradient)): 0 band kernels, 6 plane kernels, 7 image loop
+    (2, 24, 16, 16, 3, 1, (6, 6, 6)), (2, 40, 16, 16, 5, 2, (6, 6, 7)), (3, 16, 7, 7, 5, 1, (0, 0, 7)), (2, 8, 40, 40, 3, 2, (0, 0, 7)),
+    (1, 6, 15, 13, 5, 2, (0, 0, 0)), (1, 4, 64, 64, 5, 1, (6, 6, 6)), (2, 100, 8, 8, 3, 1, (6, 6, 6)), (1, 3, 130, 70, 3, 1, (0, 0, 0)),
+    # small square planes at stride 1: one wave per channel walks a chunk of the batch (ragged chunks, 4 planes per pass at 8 x 8)
+    (33, 12, 16, 16, 5, 1, (6, 6, 6)), (37, 10, 8, 8, 5, 1, (6, 6, 6)), (9, 6, 8, 8, 3, 1, (6, 6, 6)), (5, 70, 16, 16, 3, 1, (6, 6, 6)),
+    (5, 10, 32, 32, 5, 1, (6, 6, 6)), (3, 6, 32, 32, 3, 1, (6, 6, 6)),
+    # row bands of 16 / 8 rows with halo rows from the neighbouring bands
+    (3, 6, 64, 64, 3, 1, (6, 6, 6)), (5, 9, 64, 64, 5, 1, (6, 6, 6)), (2, 5, 128, 128, 3, 1, (6, 6, 6)),
+    # stride 2 on even planes (the weight gradient has no plane kernel at stride 2: band kernel or image loop)
+    (3, 6, 128, 128, 3, 2, (6, 6, 0)), (5, 7, 64, 64, 5, 2, (6, 6, 0)), (9, 5, 32, 32, 3, 2, (6, 6, 7)), (4, 6, 32, 32, 5, 2, (6, 6, 7)),
+    (6, 5, 16, 16, 3, 2, (6, 6, 7))]
 
 
 def _dw_geo(B, C, H, W, K, S):
@@ -750,8 +780,8 @@ def _dw_geo(B, C, H, W, K, S):
 @pytest.mark.parametrize("geo", DW_GEOS)
 @pytest.mark.parametrize("pro", [0, 2])
 def test_dwconv_fwd(geo, pro):
-    B, C, H, W, K, S = geo
-    g, Ho, Wo = _dw_geo(*geo)
+    B, C, H, W, K, S, fam = geo
+    g, Ho, Wo = _dw_geo(*geo[:6])
     c = Case(1)
     x = c.t("x", (B, C, H, W))
     bnv = c.bnv("bnv", C) if pro else None
@@ -759,14 +789,15 @@ def test_dwconv_fwd(geo, pro):
     y = c.t("y", (B, C, Ho, Wo), "nan")
     nrep = D.stats_replicas(C)
     st = c.t("stats", (nrep, 2, C), "zeros", "f64")
-    c.run("DWCONV_FWD", ["y", "stats"], 1e-4, sum0=("stats",), X=x, BNV=bnv, WT=w, Y=y, STATS=st, PRO=pro, NREP=nrep, **g)
+    c.run("DWCONV_FWD", ["y", "stats"], 1e-4, sum0=("stats",), want_variant=fam[0], X=x, BNV=bnv, WT=w, Y=y, STATS=st, PRO=pro, NREP=nrep,
+          **g)
 
 
 @pytest.mark.parametrize("geo", DW_GEOS)
 @pytest.mark.parametrize("pro,beta", [(0, 0), (0, 1), (2, 0)])
 def test_dwconv_dgrad(geo, pro, beta):
-    B, C, H, W, K, S = geo
-    g, Ho, Wo = _dw_geo(*geo)
+    B, C, H, W, K, S, fam = geo
+    g, Ho, Wo = _dw_geo(*geo[:6])
     c = Case(2)
     dy = c.t("dy", (B, C, Ho, Wo))
     w = c.t("w", (C, K, K), scale=0.3)
@@ -776,21 +807,21 @@ def test_dwconv_dgrad(geo, pro, beta):
     nrep = D.stats_replicas(C)
     st = c.t("stats2", (nrep, 2, C), "zeros", "f64") if pro else None
     outs = ["g"] + (["stats2"] if pro else [])
-    c.run("DWCONV_DGRAD", outs, 1e-4, sum0=("stats2",), DY=dy, WT=w, XRAW=xr, BNV=bnv, G=gg, STATS2=st, PRO=pro, BETA=beta,
+    c.run("DWCONV_DGRAD", outs, 1e-4, sum0=("stats2",), want_variant=fam[1], DY=dy, WT=w, XRAW=xr, BNV=bnv, G=gg, STATS2=st, PRO=pro, BETA=beta,
           NREP=nrep, **g)
 
 
 @pytest.mark.parametrize("geo", DW_GEOS)
 @pytest.mark.parametrize("pro", [0, 2])
 def test_dwconv_wgrad(geo, pro):
-    B, C, H, W, K, S = geo
-    g, Ho, Wo = _dw_geo(*geo)
+    B, C, H, W, K, S, fam = geo
+    g, Ho, Wo = _dw_geo(*geo[:6])
     c = Case(3)
     dy = c.t("dy", (B, C, Ho, Wo))
     x = c.t("x", (B, C, H, W))
     bnv = c.bnv("bnv", C) if pro else None
     dw = c.t("dw", (C, K, K), "randn")
-    c.run("DWCONV_WGRAD", ["dw"], 2e-4, DY=dy, X=x, BNV=bnv, DW=dw, PRO=pro, **g)
+    c.run("DWCONV_WGRAD", ["dw"], 2e-4, want_variant=fam[2], DY=dy, X=x, BNV=bnv, DW=dw, PRO=pro, **g)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1160,11 +1191,11 @@ def _fold_fields(c: "Case", C: int, n: int, nrep: int):
     return f, c.t("bnv", (4, C), "nan")
 
 
-@pytest.mark.parametrize("geo", [(2, 48, 32, 32, 3, 1), (2, 20, 17, 17, 5, 2), (3, 600, 8, 8, 5, 1), (1, 70, 64, 64, 3, 2), (4, 7, 4, 4, 3, 1),
-                                 (19, 9, 16, 16, 5, 1), (21, 5, 8, 8, 3, 1)])
+@pytest.mark.parametrize("geo", [(2, 48, 32, 32, 3, 1, 6), (2, 20, 17, 17, 5, 2, 0), (3, 600, 8, 8, 5, 1, 6), (1, 70, 64, 64, 3, 2, 6),
+                                 (4, 7, 4, 4, 3, 1, 0), (19, 9, 16, 16, 5, 1, 6), (21, 5, 8, 8, 3, 1, 6)])      # (..., kernel family)
 def test_dwconv_fwd_with_folded_bn_finalize(geo):
-    B, C, H, W, K, S = geo
-    g, Ho, Wo = _dw_geo(*geo)
+    B, C, H, W, K, S, fam = geo
+    g, Ho, Wo = _dw_geo(*geo[:6])
     c = Case(31)
     x = c.t("x", (B, C, H, W))
     w = c.t("w", (C, K, K), scale=0.3)
@@ -1172,7 +1203,8 @@ def test_dwconv_fwd_with_folded_bn_finalize(geo):
     nrep = D.stats_replicas(C)
     st = c.t("stats", (nrep, 2, C), "zeros", "f64")
     fold, bnv = _fold_fields(c, C, B * H * W, nrep)
-    c.run("DWCONV_FWD", ["y", "stats", "bnv", "frm", "frv"], 1e-4, sum0=("stats",), X=x, BNV=bnv, WT=w, Y=y, STATS=st, PRO=2, NREP=nrep, **fold, **g)
+    c.run("DWCONV_FWD", ["y", "stats", "bnv", "frm", "frv"], 1e-4, sum0=("stats",), want_variant=fam, X=x, BNV=bnv, WT=w, Y=y, STATS=st, PRO=2,
+          NREP=nrep, **fold, **g)
 
 
 @pytest.mark.parametrize("B,C,HW", [(2, 48, 256), (3, 20, 49), (1, 5, 9000), (2, 3000, 64), (7, 100, 64), (33, 9, 16), (5, 300, 196), (2, 7, 8192)])

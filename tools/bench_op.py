@@ -118,7 +118,7 @@ def main():
     torch.cuda.synchronize()
     dt = e0.elapsed_time(e1) * 1e-3 / (a.iters * R)
     ms_ev, var = _lib.profile_variants(packed, bases, st_)     # HIP-event time of the stage alone + the kernel family it took
-    fam = ("generic", "producer/consumer", "bf16", "dma-ring", "quad")[int(var[-1])] if int(var[-1]) < 5 else "-"
+    fam = ("generic", "producer/consumer", "bf16", "dma-ring", "quad", "f32-split", "dw-plane", "dw-image-loop")[int(var[-1])] if int(var[-1]) < 8 else "-"
     print(f"{a.what} B={B} M={M} C={C} H={H} pro={a.pro}: {dt * 1e3:.3f} ms  {flops / dt / 1e12:.1f} TF/s   [{fam}; events: {float(ms_ev[-1]) * 1e3:.1f} us]")
     L = _lib.lib()
     if hasattr(L, "s2k_debug_dma_counters") and fam in ("dma-ring", "quad"):     # tuning build: in-kernel stamps of the LDS-DMA ring kernel
