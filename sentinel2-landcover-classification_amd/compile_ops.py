@@ -4,8 +4,11 @@ The reference wraps its network in `torch.compile(model=self.net, mode="max-auto
 (/root/reference/src/train_segmentation.py:70-75, train_mae_prithvi.py:59-64).  Dynamo cannot trace through the ctypes launches
 and the planning code of the s2k engine - and it must not: the network IS one native program.  When a module's `forward` runs
 under `torch.compiler.is_compiling()`, it therefore calls `torch.ops.s2lc.unet_fwd` instead of the eager path: one graph node
-with a fake (meta) implementation, whose eager implementation plans / launches exactly as `engine.run_unet` does.  Its autograd
-formula is a second custom op (`s2lc::unet_bwd`), so AOTAutograd's backward graph is one node too.
+with a fake (meta) implementation, whose eager implementation plans / launches through the functions `engine.run_unet` uses
+(`engine.unet_prepare`, `engine.unet_backward_raw`; `vit_engine.vit_prepare`, `vit_engine.vit_backward_raw` for the Prithvi
+modules).  Its autograd formula is a second custom op (`s2lc::unet_bwd`), so AOTAutograd's backward graph is one node too.
+This file holds only what belongs to that boundary: handles, the forwards parked for their backward, fake implementations,
+autograd registration.
 
 What the ops hide from the compiler, on purpose:
   * the module (parameters, engines, gradient buffers) travels as an integer handle into a weak registry - the flat parameter
@@ -20,6 +23,8 @@ from __future__ import annotations
 import weakref
 
 import torch
+
+from . import engine, vit_engine
 
 _MODULES: "weakref.WeakValueDictionary[int, torch.nn.Module]" = weakref.WeakValueDictionary()
 _STATE: dict = {}          # (handle, data_ptr of the forward's output) -> (engine, lease, noise): consumed by the backward op
@@ -52,28 +57,11 @@ def _module(h: int):
 
 @torch.library.custom_op("s2lc::unet_fwd", mutates_args=())
 def unet_fwd(x: torch.Tensor, anchor: torch.Tensor, handle: int, ncls: int, want_bwd: bool, want_dx: bool) -> torch.Tensor:
-    from . import _lib
-    from .engine import _engine, _stream
-
     module = _module(handle)
-    if not x.is_cuda:
-        raise RuntimeError("EfficientnetUnet runs on the HIP engine only: move the module and the input to the GPU")
-    if x.dtype != torch.float32:
-        raise TypeError("the parity path computes in fp32; got " + str(x.dtype))
     x = x.contiguous()
-    training = module.training
-    eng = _engine(module, x, training, training or want_bwd, want_dx)
-    noise = None
-    if training:
-        noise = module.drop_connect_noise
-        if noise is None:
-            noise = torch.rand(eng.n_noise_rows, x.shape[0], device=x.device, dtype=torch.float32)
-        else:
-            noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
-        module._flat_nbt += 1
+    eng, noise = engine.unet_prepare(module, x, want_bwd, want_dx)
     out = torch.empty(eng.plan.logits_shape, dtype=torch.float32, device=x.device)
-    lease = eng.spaces.lease()
-    _lib.run(eng.fwd, eng.bases(module, x, out, noise=noise, space=lease.space), _stream(x.device))
+    lease = eng.run_forward(module, x, out, noise)
     if want_bwd:
         _park(handle, (handle, out.data_ptr()), (eng, lease, noise))
     else:
@@ -90,36 +78,14 @@ def _(x, anchor, handle, ncls, want_bwd, want_dx):
 # compiler treats the op as functional, and a backward graph in which nobody uses its outputs would be dead code.
 @torch.library.custom_op("s2lc::unet_bwd", mutates_args=())
 def unet_bwd(dout: torch.Tensor, x: torch.Tensor, out: torch.Tensor, handle: int, want_dx: bool) -> tuple[torch.Tensor, torch.Tensor]:
-    from . import _lib
-    from .engine import _stream, run_backward
-
     module = _module(handle)
     st = _STATE.pop((handle, out.data_ptr()), None)
     if st is None:
         raise RuntimeError("s2lc::unet_bwd: no saved forward for this output (backward through the same forward a second time, or "
                            "the compiled graph copied the forward's output)")
     eng, lease, noise = st
-    dout = dout.contiguous()
-    scale = getattr(module, "_grad_scale", 1.0)
-    if scale != 1.0:
-        dout = dout * scale
-    live = module._grads_live()
-    accumulate = live and not getattr(module, "_overwrite_next", False)
-    module._overwrite_next = False
-    grads = module._grad_buffer() if not accumulate else module._grad_scratch()
-    grads.zero_()
-    dx = torch.empty_like(x) if want_dx else x.new_empty((0,))
-    bases = eng.bases(module, x.contiguous(), None, dout=dout, noise=noise, grads=grads, space=lease.space, dx=dx if want_dx else None)
-    with torch.cuda.device(x.device):
-        run_backward(module, eng.bwd_marks, len(eng.bwd), lambda a, b: _lib.run(eng.bwd, bases, _stream(x.device), a, b), grads, accumulate)
-    lease.release()
-    if accumulate:
-        module._grad_buffer().add_(grads)
-    if not live:
-        module._publish_grads(module._no_grad_params)
-    if want_dx and scale != 1.0:
-        dx.mul_(1.0 / scale)
-    return dx, torch.zeros((), dtype=torch.float32, device=x.device)
+    dx = engine.unet_backward_raw(module, eng, lease, noise, x.contiguous(), dout)
+    return (dx if dx is not None else x.new_empty((0,))), torch.zeros((), dtype=torch.float32, device=x.device)
 
 
 @unet_bwd.register_fake
@@ -155,18 +121,14 @@ def compiled_unet_forward(module, x: torch.Tensor) -> torch.Tensor:
 # are read inside the op, like the engines.
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _vit_fwd(handle: int, x: torch.Tensor, mask_ratio, trainable: bool, want_dx: bool, grad_enabled: bool):
-    from . import _lib
-    from .vit_engine import _stream, vit_prepare
-
     module = _module(handle)
     x = x.contiguous()
     injected = dict(noise=module.masking_noise)
     if mask_ratio is None:
         injected["drop_u"] = module.dropout_noise
-    eng, noise, primary, want_grad = vit_prepare(module, x, injected, mask_ratio, trainable, want_dx, grad_enabled)
+    eng, noise, primary, want_grad = vit_engine.vit_prepare(module, x, injected, mask_ratio, trainable, want_dx, grad_enabled)
     out = torch.empty(eng.plan.out_bytes + 256, dtype=torch.uint8, device=x.device)
-    lease = eng.spaces.lease()
-    _lib.run(eng.fwd, eng.bases(module, x, out, noise, space=lease.space), _stream(x.device))
+    lease = eng.run_forward(module, x, out, noise)
     views = {k: v.clone() for k, v in eng.views(out).items()}      # separate storages: custom-op outputs must not alias each other
     if want_grad:
         _park(handle, (handle, views[primary].data_ptr()), (eng, lease, noise, out))
@@ -176,14 +138,12 @@ def _vit_fwd(handle: int, x: torch.Tensor, mask_ratio, trainable: bool, want_dx:
 
 
 def _vit_bwd(handle: int, key_tensor: torch.Tensor, x: torch.Tensor, gouts: dict):
-    from .vit_engine import vit_backward_raw
-
     module = _module(handle)
     st = _STATE.pop((handle, key_tensor.data_ptr()), None)
     if st is None:
         raise RuntimeError("s2lc backward op: no saved forward for this output")
     eng, lease, noise, out = st
-    dx = vit_backward_raw(module, eng, lease, noise, out, x.contiguous(), gouts)
+    dx = vit_engine.vit_backward_raw(module, eng, lease, noise, out, x.contiguous(), gouts)
     return dx if dx is not None else x.new_empty((0,))
 
 

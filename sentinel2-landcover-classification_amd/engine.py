@@ -4,6 +4,12 @@ PyTorch supplies device memory, the current HIP stream and the autograd *edge* (
 `autograd.Function` for the whole network: forward = one `s2k_program_run`, backward = one more).
 The reference's equivalent is `self.net(x)` + `loss.backward()` in
 /root/reference/src/train_segmentation.py:129-147 dispatching ~1,000 ATen ops per step.
+
+One of each, for every model family and both entry points (eager autograd nodes; the torch.compile custom ops of compile_ops.py):
+`Engine` (buffers + packed programs; `UnetEngine` here, `VitEngine` / `MethodEngine` in vit_engine.py only say how their plan is
+made), `preflight`, `fill_noise`, `run_backward` (how a backward meets the data-parallel reducer) and `backward_into_grads` (the
+gradient target around it).  The U-Net's step is `unet_prepare` + `Engine.run_forward` + `unet_backward_raw`, as the ViTs' is
+`vit_engine.vit_prepare` / `vit_backward_raw`.
 """
 from __future__ import annotations
 
@@ -58,13 +64,23 @@ class WorkspacePool:
         return self.free[-1]
 
 
-class UnetEngine:
-    """Buffers + packed programs for one (B, H, W, training) shape of one module."""
+_TORCH_DT = {"f32": torch.float32, "i64": torch.int64, "i32": torch.int32}
 
-    def __init__(self, module, B: int, H: int, W: int, training: bool, device: torch.device, want_bwd: bool | None = None,
-                 want_dx: bool = False):
-        plan = module._make_plan(B, H, W, training, want_bwd, want_dx)
-        self.want_dx = want_dx
+
+def _stream(device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _view(buf: torch.Tensor, t) -> torch.Tensor:
+    """The tensor a TRef names inside a packed byte buffer (OUT / X / DOUT / DX)."""
+    return buf[t.off:t.off + t.nbytes].view(_TORCH_DT[t.dtype]).view(t.shape)
+
+
+class Engine:
+    """Buffers + packed programs of one planned network for one cache key of one module.  The subclasses only say how their
+    plan is made and keep what is particular to their family."""
+
+    def __init__(self, plan, device: torch.device):
         self.plan = plan
         self.fwd = plan.fwd.pack()
         self.bwd = plan.bwd.pack() if plan.bwd is not None else None
@@ -73,9 +89,8 @@ class UnetEngine:
         self.const = torch.tensor(plan.const_table if plan.const_table else [0] * 8, dtype=torch.int32, device=device)
         self.wpack = torch.zeros(plan.wpack_bytes // 4 + 65536, dtype=torch.float32, device=device)  # + slack: A-tile loads may overrun
         self.wgs = torch.empty(plan.layout.n_params, dtype=torch.float32, device=device) if plan.bwd is not None else None
-        self.n_noise_rows = plan.n_noise_rows
-        self.B = B
         self.bwd_marks = plan.bwd_param_marks
+        self.want_dx = getattr(plan, "want_dx", False)     # the backward program also writes the input's gradient into DX
 
     @property
     def resident(self) -> Workspace:
@@ -90,7 +105,8 @@ class UnetEngine:
     def aux(self) -> torch.Tensor:
         return self.resident.aux
 
-    def bases(self, module, x, out, dout=None, noise=None, grads=None, space: Workspace | None = None, dx=None) -> _lib.Bases:
+    def bases(self, module, x, out, noise=None, dout=None, grads=None, space: Workspace | None = None, dx=None,
+              dout_need: int | None = None) -> _lib.Bases:
         space = space or self.resident
         b = _lib.Bases()
         b.set("WS", space.ws).set("AUX", space.aux).set("CONST", self.const).set("WPACK", self.wpack)
@@ -99,7 +115,9 @@ class UnetEngine:
         if self.wgs is not None:
             b.set("WGS", self.wgs)
         if dout is not None:
-            need = 4 * int(torch.Size(self.plan.logits_shape).numel())
+            plan, need = self.plan, dout_need     # dout_need: the stages reading the rest of the packed buffer are skipped by the caller
+            if need is None:
+                need = getattr(plan, "dout_bytes", 0) or 4 * int(torch.Size(getattr(plan, "dout_shape", None) or plan.logits_shape).numel())
             if dout.numel() * dout.element_size() < need:      # the backward program reads DOUT unchecked on the device
                 raise ValueError(f"DOUT holds {dout.numel() * dout.element_size()} bytes, the backward program reads {need}")
             b.set("DOUT", dout)
@@ -111,9 +129,24 @@ class UnetEngine:
             b.set("DX", dx)
         return b
 
+    def views(self, out: torch.Tensor) -> dict:
+        return {name: _view(out, t) for name, t in self.plan.outputs.items()}
 
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+    def run_forward(self, module, x, out, noise) -> WorkspaceLease:
+        """Enqueue the forward program on a leased workspace; the caller keeps the lease until the backward has run, or releases
+        it at once (stream-ordered: the next forward that takes this workspace is enqueued behind this one)."""
+        lease = self.spaces.lease()
+        _lib.run(self.fwd, self.bases(module, x, out, noise, space=lease.space), _stream(x.device))
+        return lease
+
+
+class UnetEngine(Engine):
+    """One (B, H, W, training) shape of an EfficientnetUnet."""
+
+    def __init__(self, module, B: int, H: int, W: int, training: bool, device: torch.device, want_bwd: bool | None = None,
+                 want_dx: bool = False):
+        super().__init__(module._make_plan(B, H, W, training, want_bwd, want_dx), device)
+        self.want_dx, self.B, self.n_noise_rows = want_dx, B, self.plan.n_noise_rows
 
 
 def _engine(module, x: torch.Tensor, training: bool, want_bwd: bool, want_dx: bool = False) -> UnetEngine:
@@ -126,6 +159,34 @@ def _engine(module, x: torch.Tensor, training: bool, want_bwd: bool, want_dx: bo
     return eng
 
 
+def preflight(module, x) -> None:
+    """What every whole-network forward checks before it plans or launches anything."""
+    if not x.is_cuda:
+        raise RuntimeError(f"{type(module).__name__} runs on the HIP engine only: move the module and the input to the GPU "
+                           "(there is no CPU fallback; the CPU restatement lives under oracle/ for tests)")
+    _lib.lib()
+    if x.dtype != torch.float32:
+        raise TypeError("the parity path computes in fp32; got " + str(x.dtype))
+    if module._flat_params.device != x.device:
+        raise RuntimeError("module and input are on different devices")
+
+
+def fill_noise(plan, injected: dict | None, device) -> torch.Tensor:
+    """The NOISE buffer of a plan: fresh uniforms, or the tensors injected by name (parity tests)."""
+    noise = torch.empty(max(plan.noise_bytes // 4, 1), dtype=torch.float32, device=device)
+    for name, t in plan.noise.items():
+        n = int(np.prod(t.shape))
+        dst = noise[t.off // 4:t.off // 4 + n]
+        src = (injected or {}).get(name)
+        if src is None:
+            dst.uniform_(0.0, 1.0)     # torch.rand semantics: U[0, 1)
+        else:
+            if tuple(src.shape) != tuple(t.shape):
+                raise ValueError(f"{name} must have shape {tuple(t.shape)}, got {tuple(src.shape)}")
+            dst.copy_(src.to(device=device, dtype=torch.float32).reshape(-1))
+    return noise
+
+
 class _UnetFunction(torch.autograd.Function):
     """Whole-network autograd node.  Parameter gradients are written straight into the module's
     flat gradient buffer by the backward program (never returned through autograd: 900+
@@ -134,44 +195,64 @@ class _UnetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, anchor, module, eng, noise):
         out = torch.empty(eng.plan.logits_shape, dtype=torch.float32, device=x.device)
-        lease = eng.spaces.lease()
-        bases = eng.bases(module, x, out, noise=noise, space=lease.space)
-        _lib.run(eng.fwd, bases, _stream(x.device))
-        ctx.module, ctx.eng, ctx.noise, ctx.lease = module, eng, noise, lease
+        ctx.module, ctx.eng, ctx.noise, ctx.lease = module, eng, noise, eng.run_forward(module, x, out, noise)
         ctx.save_for_backward(x)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        module, eng, lease = ctx.module, ctx.eng, ctx.lease
-        if lease.space is None:
-            raise RuntimeError("backward through the same forward a second time: the saved activations have been released "
-                               "(the s2k engine keeps them for one backward, like autograd without retain_graph)")
         (x,) = ctx.saved_tensors
-        dout = dout.contiguous()
-        scale = getattr(module, "_grad_scale", 1.0)
-        if scale != 1.0:
-            dout = dout * scale   # data-parallel mean folded into the upstream gradient
-        live = module._grads_live()
-        accumulate = live and not getattr(module, "_overwrite_next", False)
-        module._overwrite_next = False
-        grads = module._grad_buffer() if not accumulate else module._grad_scratch()
-        grads.zero_()
-        dx = torch.empty_like(x) if eng.want_dx else None      # gradient w.r.t. the input (planned only when x.requires_grad)
-        bases = eng.bases(module, x, None, dout=dout, noise=ctx.noise, grads=grads, space=lease.space, dx=dx)
-        st = _stream(x.device)
-        with torch.cuda.device(x.device):
-            run_backward(module, eng.bwd_marks, len(eng.bwd), lambda a, b: _lib.run(eng.bwd, bases, st, a, b), grads, accumulate)
-        lease.release()     # stream-ordered: the next forward that takes this workspace is enqueued behind this backward
-        if accumulate:
-            module._grad_buffer().add_(grads)
-        if not live:
-            module._publish_grads(module._no_grad_params)
-        if dx is not None and scale != 1.0:
-            # the 1/world of the data-parallel mean belongs to the PARAMETER gradients only: whatever sits in front of the
-            # module (an input adapter under its own DDP, a saliency map) must see d loss_rank / d x, as with torch DDP
-            dx.mul_(1.0 / scale)
-        return dx, None, None, None, None
+        return unet_backward_raw(ctx.module, ctx.eng, ctx.lease, ctx.noise, x, dout), None, None, None, None
+
+
+def unet_backward_raw(module, eng, lease, noise, x, dout):
+    """The backward program of a UnetEngine forward.  Parameter gradients go into the module's flat gradient buffer; returns dX
+    or None.  Shared by the autograd node above and the torch.compile custom op (compile_ops.py)."""
+    if lease.space is None:
+        raise RuntimeError("backward through the same forward a second time: the saved activations have been released "
+                           "(the s2k engine keeps them for one backward, like autograd without retain_graph)")
+    dout = dout.contiguous()
+    scale = getattr(module, "_grad_scale", 1.0)
+    if scale != 1.0:
+        dout = dout * scale   # data-parallel mean folded into the upstream gradient
+    return backward_into_grads(module, eng, lease, x, None, noise, dout, scale)
+
+
+def backward_into_grads(module, eng, lease, x, out, noise, dout, scale: float, skip=(), dout_need: int | None = None):
+    """A whole-network backward program and its gradient target (the U-Net's and the ViTs').  Gradients that are live (a second
+    backward before zero_grad) are accumulated: the program writes the scratch buffer, which is then added to the flat gradient
+    buffer; otherwise the program overwrites the flat buffer, and parameters that had no `.grad` yet get theirs published.
+    `skip`: sorted stage ranges [s0, s1) left out of the program.  Returns dX (planned only when x.requires_grad) or None."""
+    live = module._grads_live()
+    accumulate = live and not getattr(module, "_overwrite_next", False)
+    module._overwrite_next = False
+    grads = module._grad_scratch() if accumulate else module._grad_buffer()
+    grads.zero_()
+    dx = torch.empty_like(x) if eng.want_dx else None
+    bases = eng.bases(module, x, out, noise, dout=dout, grads=grads, space=lease.space, dx=dx, dout_need=dout_need)
+    st = _stream(x.device)
+
+    def run_range(a, b):        # stages [a, b) of the backward program minus the skipped ranges
+        for (s0, s1) in skip:
+            if a < s1 and s0 < b:
+                if a < s0:
+                    _lib.run(eng.bwd, bases, st, a, s0)
+                a = max(a, s1)
+        if a < b:
+            _lib.run(eng.bwd, bases, st, a, b)
+
+    with torch.cuda.device(x.device):
+        run_backward(module, eng.bwd_marks, len(eng.bwd), run_range, grads, accumulate, lo_min=getattr(eng.plan, "trainable_lo", 0))
+    lease.release()     # stream-ordered: the next forward that takes this workspace is enqueued behind this backward
+    if accumulate:
+        module._grad_buffer().add_(grads)
+    if not live:
+        module._publish_grads(module._no_grad_params)
+    if dx is not None and scale != 1.0:
+        # the 1/world of the data-parallel mean belongs to the PARAMETER gradients only: whatever sits in front of the
+        # module (an input adapter under its own DDP, a saliency map) must see d loss_rank / d x, as with torch DDP
+        dx.mul_(1.0 / scale)
+    return dx
 
 
 def _note_bucket_reduction(module) -> None:
@@ -215,38 +296,33 @@ def run_backward(module, marks, n_ops: int, run_range, grads: torch.Tensor, accu
         hook(max(lo, lo_min), hi, grads)
 
 
-def run_unet(module, x: torch.Tensor) -> torch.Tensor:
-    if not x.is_cuda:
-        raise RuntimeError("EfficientnetUnet runs on the HIP engine only: move the module and the input to the GPU "
-                           "(there is no CPU fallback; the CPU restatement lives under oracle/ for tests)")
-    _lib.lib()
-    if x.dtype != torch.float32:
-        raise TypeError("the parity path computes in fp32; got " + str(x.dtype))
-    if module._flat_params.device != x.device:
-        raise RuntimeError("module and input are on different devices")
-    x = x.contiguous()
+def unet_prepare(module, x: torch.Tensor, want_bwd: bool, want_dx: bool):
+    """(engine, drop-connect noise or None) for one forward of the U-Net on a contiguous `x` (shared by run_unet and the
+    torch.compile custom op).  train() plans always carry the backward program; eval() plans only when autograd wants one (torch
+    differentiates an eval-mode module just the same: BatchNorm on its running statistics, no drop-connect)."""
+    preflight(module, x)
     training = module.training
-    # train() plans always carry the backward program; eval() plans only when autograd wants one (torch differentiates an
-    # eval-mode module just the same: BatchNorm on its running statistics, no drop-connect)
-    want_dx = torch.is_grad_enabled() and x.requires_grad
-    differentiate = torch.is_grad_enabled() and (want_dx or any(p.requires_grad for p in module.parameters()))
-    want_bwd = training or differentiate
-    eng = _engine(module, x, training, want_bwd, want_dx)
+    eng = _engine(module, x, training, training or want_bwd, want_dx)
     noise = None
     if training:
         noise = module.drop_connect_noise
         if noise is None:
             noise = torch.rand(eng.n_noise_rows, x.shape[0], device=x.device, dtype=torch.float32)
         else:
-            noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
-            if tuple(noise.shape) != (eng.n_noise_rows, x.shape[0]):
+            if tuple(noise.shape) != (eng.n_noise_rows, x.shape[0]):      # the device program reads NOISE unchecked
                 raise ValueError(f"drop_connect_noise must be [{eng.n_noise_rows}, {x.shape[0]}]")
+            noise = noise.to(device=x.device, dtype=torch.float32).contiguous()
         module._flat_nbt += 1  # every BatchNorm's num_batches_tracked (one fused add over the flat view)
+    return eng, noise
+
+
+def run_unet(module, x: torch.Tensor) -> torch.Tensor:
+    x = x.contiguous()
+    want_dx = torch.is_grad_enabled() and x.requires_grad
+    differentiate = torch.is_grad_enabled() and (want_dx or any(p.requires_grad for p in module.parameters()))
+    eng, noise = unet_prepare(module, x, differentiate, want_dx)
     if differentiate:
-        anchor = module._anchor(x.device)
-        return _UnetFunction.apply(x, anchor, module, eng, noise)
+        return _UnetFunction.apply(x, module._anchor(x.device), module, eng, noise)
     out = torch.empty(eng.plan.logits_shape, dtype=torch.float32, device=x.device)
-    lease = eng.spaces.lease()
-    _lib.run(eng.fwd, eng.bases(module, x, out, noise=noise, space=lease.space), _stream(x.device))
-    lease.release()
+    eng.run_forward(module, x, out, noise).release()
     return out

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .engine import _stream
 from .plan import opdefs as D
 from .plan.program import Program, TRef
 
@@ -27,10 +28,6 @@ class LossType(str, enum.Enum):
     FOCAL = "focal"
     DICE = "dice"
     DICE_FOCAL = "dice_focal"
-
-
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _check(logits: torch.Tensor, y: torch.Tensor):

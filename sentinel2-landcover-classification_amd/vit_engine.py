@@ -1,73 +1,20 @@
 """Runtime glue for the Prithvi modules (MaskedAutoencoderViT, PrithviSegmentationNet): device buffers of a planned
-network + one autograd node around its two stage programs.  Mirrors engine.py (the U-Net's); PyTorch supplies device
-memory, the HIP stream and the autograd edge only."""
+network + one autograd node around its two stage programs, and the separately callable methods.  The engine class, the
+gradient target of a backward, the noise fill and the pre-flight checks are engine.py's, shared with the U-Net."""
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from . import _lib
-from .engine import Workspace, WorkspacePool, run_backward
-
-_TORCH_DT = {"f32": torch.float32, "i64": torch.int64, "i32": torch.int32}
+from .engine import _TORCH_DT, Engine, _stream, _view, backward_into_grads, fill_noise, preflight
 
 
-class VitEngine:
+class VitEngine(Engine):
+    """One (B, training, mask ratio) shape of a MaskedAutoencoderViT / PrithviSegmentationNet."""
+
     def __init__(self, module, B: int, training: bool, mask_ratio: float, device: torch.device, want_bwd: bool | None = None,
                  want_dx: bool = False):
-        plan = module._make_plan(B, training, mask_ratio, want_bwd, want_dx)
-        self.plan = plan
-        self.fwd = plan.fwd.pack()
-        self.bwd = plan.bwd.pack() if plan.bwd is not None else None
-        self.spaces = WorkspacePool(plan.ws_bytes, plan.aux_bytes, device)
-        self.const = torch.tensor(plan.const_table if plan.const_table else [0] * 8, dtype=torch.int32, device=device)
-        self.wpack = torch.zeros(plan.wpack_bytes // 4 + 65536, dtype=torch.float32, device=device)
-        self.wgs = torch.empty(plan.layout.n_params, dtype=torch.float32, device=device) if plan.bwd is not None else None
-        self.bwd_marks = plan.bwd_param_marks
-
-    @property
-    def resident(self) -> Workspace:
-        return self.spaces.peek()
-
-    @property
-    def ws(self) -> torch.Tensor:
-        return self.resident.ws
-
-    @property
-    def aux(self) -> torch.Tensor:
-        return self.resident.aux
-
-    def bases(self, module, x, out, noise, dout=None, grads=None, space: Workspace | None = None, dx=None, dout_need: int | None = None) -> _lib.Bases:
-        space = space or self.resident
-        b = _lib.Bases()
-        b.set("WS", space.ws).set("AUX", space.aux).set("CONST", self.const).set("WPACK", self.wpack)
-        b.set("PARAMS", module._flat_params).set("BUFS", module._flat_bufs)
-        b.set("X", x).set("OUT", out).set("NOISE", noise)
-        if self.wgs is not None:
-            b.set("WGS", self.wgs)
-        if dout is not None:
-            plan = self.plan
-            need = plan.dout_bytes if plan.dout_bytes else 4 * int(torch.Size(plan.dout_shape).numel())
-            if dout_need is not None:
-                need = dout_need       # the stages reading the rest of the packed buffer are skipped by the caller
-            if dout.numel() * dout.element_size() < need:      # the backward program reads DOUT unchecked on the device
-                raise ValueError(f"DOUT holds {dout.numel() * dout.element_size()} bytes, the backward program reads {need}")
-            b.set("DOUT", dout)
-        if grads is not None:
-            b.set("GRADS", grads)
-        if dx is not None:
-            b.set("DX", dx)
-        return b
-
-    def views(self, out: torch.Tensor) -> dict:
-        res = {}
-        for name, t in self.plan.outputs.items():
-            res[name] = out[t.off:t.off + t.nbytes].view(_TORCH_DT[t.dtype]).view(t.shape)
-        return res
-
-
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+        super().__init__(module._make_plan(B, training, mask_ratio, want_bwd, want_dx), device)
 
 
 class _VitFunction(torch.autograd.Function):
@@ -77,8 +24,7 @@ class _VitFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, anchor, module, eng, noise, primary):
         out = torch.empty(eng.plan.out_bytes + 256, dtype=torch.uint8, device=x.device)
-        lease = eng.spaces.lease()     # held until the backward has run (engine.py, Workspace)
-        _lib.run(eng.fwd, eng.bases(module, x, out, noise, space=lease.space), _stream(x.device))
+        lease = eng.run_forward(module, x, out, noise)     # held until the backward has run (engine.py, Workspace)
         v = eng.views(out)
         names = [primary] + [n for n in v if n != primary]
         ctx.module, ctx.eng, ctx.noise, ctx.names, ctx.out, ctx.lease = module, eng, noise, names, out, lease
@@ -116,7 +62,7 @@ def vit_backward_raw(module, eng, lease, noise, out, x, gouts: dict):
         for name, g in gouts.items():
             if g is not None and name in plan.douts:
                 t = plan.douts[name]
-                dst = buf[t.off:t.off + t.nbytes].view(torch.float32).view(t.shape)
+                dst = _view(buf, t)
                 dst.copy_(g.reshape(t.shape))
                 if scale != 1.0:
                     dst.mul_(scale)
@@ -125,47 +71,13 @@ def vit_backward_raw(module, eng, lease, noise, out, x, gouts: dict):
         dout = gouts[primary].contiguous().reshape(plan.dout_shape).to(torch.float32)
         if scale != 1.0:
             dout = dout * scale
-    live = module._grads_live()
-    accumulate = live and not getattr(module, "_overwrite_next", False)
-    module._overwrite_next = False
-    grads = module._grad_buffer() if not accumulate else module._grad_scratch()
-    grads.zero_()
-    dx = torch.empty_like(x) if plan.want_dx else None
-    bases = eng.bases(module, x, out, noise, dout=dout, grads=grads, space=lease.space, dx=dx, dout_need=dout_need)
-    st = _stream(x.device)
-
-    def run_range(a, b):        # stages [a, b) of the backward program minus the skipped ranges
-        for (s0, s1) in skip:
-            if a < s1 and s0 < b:
-                if a < s0:
-                    _lib.run(eng.bwd, bases, st, a, s0)
-                a = max(a, s1)
-        if a < b:
-            _lib.run(eng.bwd, bases, st, a, b)
-
-    with torch.cuda.device(x.device):
-        run_backward(module, eng.bwd_marks, len(eng.bwd), run_range, grads, accumulate, lo_min=eng.plan.trainable_lo)
-    lease.release()
-    if accumulate:
-        module._grad_buffer().add_(grads)
-    if not live:
-        module._publish_grads(module._no_grad_params)
-    if dx is not None and scale != 1.0:
-        dx.mul_(1.0 / scale)       # the data-parallel 1/world applies to parameter gradients only (engine.py)
-    return dx
+    return backward_into_grads(module, eng, lease, x, out, noise, dout, scale, skip, dout_need)
 
 
 def vit_prepare(module, x: torch.Tensor, injected: dict, mask_ratio: float | None, trainable: bool, want_dx: bool, grad_enabled: bool):
     """(engine, noise buffer, primary output name, want_grad) for one forward: plan selection exactly as the reference's modules
     behave under torch autograd (shared by run_vit and the torch.compile custom ops)."""
-    if not x.is_cuda:
-        raise RuntimeError(f"{type(module).__name__} runs on the HIP engine only: move the module and the input to the GPU "
-                           "(there is no CPU fallback; the CPU restatement lives under oracle/ for tests)")
-    _lib.lib()
-    if x.dtype != torch.float32:
-        raise TypeError("the parity path computes in fp32; got " + str(x.dtype))
-    if module._flat_params.device != x.device:
-        raise RuntimeError("module and input are on different devices")
+    preflight(module, x)
     B = x.shape[0]
     is_seg = mask_ratio is None
     # the segmentation head has BatchNorm / Dropout2d: its plan follows module.training (train() plans always carry the
@@ -180,18 +92,7 @@ def vit_prepare(module, x: torch.Tensor, injected: dict, mask_ratio: float | Non
     if eng is None:
         eng = VitEngine(module, B, training, mr, x.device, want_bwd, want_dx)
         module._engines[key] = eng
-    plan = eng.plan
-    noise = torch.empty(max(plan.noise_bytes // 4, 1), dtype=torch.float32, device=x.device)
-    for name, t in plan.noise.items():
-        n = int(np.prod(t.shape))
-        dst = noise[t.off // 4:t.off // 4 + n]
-        src = injected.get(name)
-        if src is None:
-            dst.uniform_(0.0, 1.0)     # torch.rand semantics: U[0, 1)
-        else:
-            if tuple(src.shape) != tuple(t.shape):
-                raise ValueError(f"{name} must have shape {tuple(t.shape)}, got {tuple(src.shape)}")
-            dst.copy_(src.to(device=x.device, dtype=torch.float32).reshape(-1))
+    noise = fill_noise(eng.plan, injected, x.device)
     if is_seg and training:
         module._flat_nbt += 1
     return eng, noise, ("logits" if is_seg else "loss"), want_grad
@@ -210,9 +111,7 @@ def run_vit(module, x: torch.Tensor, injected: dict, mask_ratio: float | None = 
         names = [primary] + [n for n in plan.outputs if n != primary]
         return dict(zip(names, outs))
     out = torch.empty(plan.out_bytes + 256, dtype=torch.uint8, device=x.device)
-    lease = eng.spaces.lease()
-    _lib.run(eng.fwd, eng.bases(module, x, out, noise, space=lease.space), _stream(x.device))
-    lease.release()
+    eng.run_forward(module, x, out, noise).release()
     return eng.views(out)
 
 
@@ -222,35 +121,10 @@ def run_vit(module, x: torch.Tensor, injected: dict, mask_ratio: float | None = 
 # buffer, upstream gradients into one DOUT buffer, input gradients come back in a DX buffer; parameter gradients are
 # ADDED to the module's flat gradient buffer (several method nodes run in one backward pass: encoder, decoder, loss).
 # ---------------------------------------------------------------------------------------------------------------------
-class MethodEngine:
-    def __init__(self, plan, device: torch.device):
-        self.plan = plan
-        self.fwd = plan.fwd.pack()
-        self.bwd = plan.bwd.pack() if plan.bwd is not None else None
-        self.spaces = WorkspacePool(plan.ws_bytes, plan.aux_bytes, device)
-        self.const = torch.tensor(plan.const_table if plan.const_table else [0] * 8, dtype=torch.int32, device=device)
-        self.wpack = torch.zeros(plan.wpack_bytes // 4 + 65536, dtype=torch.float32, device=device)
-        self.wgs = torch.empty(plan.layout.n_params, dtype=torch.float32, device=device) if plan.bwd is not None else None
-        self.bwd_marks = plan.bwd_param_marks
-
-    def bases(self, module, space, xbuf, out, noise, dout=None, grads=None, dx=None) -> _lib.Bases:
-        b = _lib.Bases()
-        b.set("WS", space.ws).set("AUX", space.aux).set("CONST", self.const).set("WPACK", self.wpack)
-        b.set("PARAMS", module._flat_params).set("BUFS", module._flat_bufs)
-        b.set("X", xbuf).set("OUT", out).set("NOISE", noise)
-        if self.wgs is not None:
-            b.set("WGS", self.wgs)
-        if dout is not None:
-            b.set("DOUT", dout)
-        if grads is not None:
-            b.set("GRADS", grads)
-        if dx is not None:
-            b.set("DX", dx)
-        return b
-
-
-def _view(buf: torch.Tensor, t) -> torch.Tensor:
-    return buf[t.off:t.off + t.nbytes].view(_TORCH_DT[t.dtype]).view(t.shape)
+class MethodEngine(Engine):
+    def __init__(self, plan, device: torch.device, publish_all: bool = False):
+        super().__init__(plan, device)
+        self.publish_all = publish_all     # every parameter of the layout may receive a gradient from this method
 
 
 class _MethodFunction(torch.autograd.Function):
@@ -263,9 +137,8 @@ class _MethodFunction(torch.autograd.Function):
             ref = plan.inputs[name]
             _view(xbuf, ref).copy_(t.to(device=dev, dtype=_TORCH_DT[ref.dtype]).reshape(ref.shape))
         out = torch.empty(plan.out_bytes + 256, dtype=torch.uint8, device=dev)
-        lease = eng.spaces.lease()
-        _lib.run(eng.fwd, eng.bases(module, lease.space, xbuf, out, noise), _stream(dev))
-        outs = tuple(_view(out, plan.outputs[n]) for n in plan.outputs)
+        lease = eng.run_forward(module, xbuf, out, noise)
+        outs = tuple(eng.views(out).values())
         ctx.module, ctx.eng, ctx.noise, ctx.names, ctx.xbuf, ctx.out, ctx.lease = module, eng, noise, names, xbuf, out, lease
         ctx.mark_non_differentiable(*[o for n, o in zip(plan.outputs, outs) if n not in plan.douts])
         if eng.bwd is None:
@@ -306,11 +179,11 @@ class _MethodFunction(torch.autograd.Function):
         module._overwrite_next = False
         scratch = module._grad_scratch()
         scratch.zero_()
-        _lib.run(eng.bwd, eng.bases(module, lease.space, ctx.xbuf, ctx.out, ctx.noise, dout=dout, grads=scratch, dx=dx), _stream(dev))
+        _lib.run(eng.bwd, eng.bases(module, ctx.xbuf, ctx.out, ctx.noise, dout=dout, grads=scratch, space=lease.space, dx=dx), _stream(dev))
         lease.release()
         main.add_(scratch, alpha=scale)
-        if not live or getattr(eng, "publish_all", False):
-            module._publish_grads(set() if getattr(eng, "publish_all", False) else module._no_grad_params)
+        if not live or eng.publish_all:
+            module._publish_grads(set() if eng.publish_all else module._no_grad_params)
         grads_in = tuple(_view(dx, plan.dins[n]).clone() if n in plan.dins else None for n in ctx.names)
         return (None, None, None, None, None) + grads_in
 
@@ -332,21 +205,10 @@ def run_method(module, key, make_plan, inputs: dict, injected: dict | None = Non
     ckey = ("method",) + tuple(key) + (needs, dev)
     eng = module._engines.get(ckey)
     if eng is None:
-        eng = MethodEngine(make_plan(needs), dev)
-        eng.publish_all = publish_all     # every parameter of the layout may receive a gradient from this method
+        eng = MethodEngine(make_plan(needs), dev, publish_all)
         module._engines[ckey] = eng
     plan = eng.plan
-    noise = torch.empty(max(plan.noise_bytes // 4, 1), dtype=torch.float32, device=dev)
-    for name, t in plan.noise.items():
-        n = int(np.prod(t.shape))
-        dst = noise[t.off // 4:t.off // 4 + n]
-        src = (injected or {}).get(name)
-        if src is None:
-            dst.uniform_(0.0, 1.0)
-        else:
-            if tuple(src.shape) != tuple(t.shape):
-                raise ValueError(f"{name} must have shape {tuple(t.shape)}, got {tuple(src.shape)}")
-            dst.copy_(src.to(device=dev, dtype=torch.float32).reshape(-1))
+    noise = fill_noise(plan, injected, dev)
     names = tuple(plan.inputs)
     for n in names:
         if tuple(inputs[n].shape) != tuple(plan.inputs[n].shape):

@@ -204,6 +204,51 @@ def test_run_backward_modes_without_a_gpu():
         run_backward(m2, marks, 5, lambda a, b: None, None, accumulate=True)
 
 
+def test_unet_prepare_checks_are_shared_by_eager_and_compiled_without_a_gpu(monkeypatch):
+    """engine.unet_prepare, the one place that checks and plans a U-Net forward (run_unet and the s2lc::unet_fwd custom op): it
+    refuses a module and an input on different devices and a drop_connect_noise that is not [n_noise_rows, B] - the device program
+    reads NOISE unchecked - before anything is moved, planned or counted; the compiled entry goes through the same function."""
+    from types import SimpleNamespace
+
+    from s2lc_amd import _lib, compile_ops, engine
+
+    monkeypatch.setattr(_lib, "lib", lambda: None)     # the checks come before any launch: no device library needed
+    dev = torch.device("cuda", 0)
+
+    class X:        # what the checks read of a contiguous fp32 tensor on a GPU
+        is_cuda, dtype, device, shape, requires_grad = True, torch.float32, dev, torch.Size((2, 4, 64, 64)), False
+
+        def contiguous(self):
+            return self
+
+    class M:
+        training, drop_connect_noise, _flat_nbt = True, None, 0
+
+        def parameters(self):
+            return []
+
+    m = M()
+    m._engines = {((2, 4, 64, 64), True, True, False, dev): SimpleNamespace(n_noise_rows=16)}
+    for entry in (lambda: engine.unet_prepare(m, X(), True, False), lambda: engine.run_unet(m, X())):
+        m._flat_params = torch.zeros(1)                         # the module stayed on the CPU
+        with pytest.raises(RuntimeError, match="^module and input are on different devices$"):
+            entry()
+        m._flat_params = SimpleNamespace(device=dev)
+        for bad in (torch.zeros(2, 16), torch.zeros(16, 3), torch.zeros(32)):
+            m.drop_connect_noise = bad
+            with pytest.raises(ValueError, match=r"^drop_connect_noise must be \[16, 2\]$"):
+                entry()
+        assert m._flat_nbt == 0
+        m.drop_connect_noise = None
+
+    calls, prepare = [], engine.unet_prepare
+    monkeypatch.setattr(engine, "unet_prepare", lambda *a: calls.append(a) or prepare(*a))
+    x = torch.zeros(2, 4, 64, 64)
+    with pytest.raises(RuntimeError, match="runs on the HIP engine only"):      # a CPU tensor: refused by unet_prepare's first check
+        torch.ops.s2lc.unet_fwd(x, torch.zeros(()), compile_ops.register(m), 4, True, False)
+    assert len(calls) == 1 and calls[0][0] is m and calls[0][2:] == (True, False)
+
+
 def test_reducer_bucket_size_is_a_planner_parameter():
     """FlatGradReducer(bucket_mb=...) reaches the planner: smaller buckets -> more backward segments, same coverage"""
     from s2lc_amd.plan.unet_plan import plan_unet
