@@ -49,6 +49,8 @@ def focal(logits, y, alpha: torch.Tensor, gamma: float, label_smoothing: float =
     pt = torch.exp(-ce)
     a = alpha.to(logits.dtype)[y]
     fl = a * (1.0 - pt) ** gamma * ce
+    if reduce_type == "none":      # (not a reference option: the per-pixel terms, for the stage oracle's f64 accumulator)
+        return fl
     return fl.mean() if reduce_type == "mean" else fl.sum()
 
 

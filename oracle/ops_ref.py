@@ -451,6 +451,18 @@ def op_loss_fwd(m: Mem, o):
     y = m.view(o["LABELS"], (B, HW, 1), "i64")
     alpha = m.view(o["ALPHA"], (C,))
     m.view(o["LOSS"], (1,)).copy_(_loss_value(lg, y, alpha, o).reshape(1))
+    acc = m.view(o["ACC"], (2,), "f64")
+    if acc is not None:     # [numerator, denominator] as LOSS_BWD reads them: per-pixel terms in the working precision, summed in f64
+        from . import losses_ref
+
+        smooth = float(np.float32(o["SMOOTH"]))
+        if o["MODE"] == 0:
+            ce, w_y, _ = losses_ref._per_pixel_ce(lg, y, alpha, smooth, o["IGNORE"])
+            acc[0], acc[1] = ce.double().sum(), w_y.double().sum()
+        else:
+            a = torch.ones(C, dtype=lg.dtype) if alpha is None else alpha
+            acc[0] = losses_ref.focal(lg, y, a, float(np.float32(o["GAMMA"])), smooth, o["IGNORE"], "none").double().sum()
+            acc[1] = 0.0
 
 
 def op_loss_bwd(m: Mem, o):

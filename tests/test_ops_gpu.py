@@ -72,23 +72,11 @@ class Case:
         fields["BF16_BASE"] = dst16.off - dst.off // 2
         return ("WEIGHT_PACK", fields), dst, MP, dst16
 
-    def run(self, kind, outputs, tol=1e-4, sum0=(), pre=(), want_variant=None, per_column=(), ref64=False, **fields):
-        """sum0: outputs compared after summing their leading (statistics-replica) dimension.
-        pre: stage records to run first (e.g. WEIGHT_PACK).  want_variant: the kernel family the stage must have taken
-        (s2k_program_profile_variants, include/s2k.h: 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads,
-        5 f32-split; depthwise: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop).
-        per_column: outputs whose every last-dim column must also meet `tol` against that column's own max |ref| (a wrong
-        column among larger ones - e.g. a ragged last channel tile - hides under the whole tensor's max).
-        ref64: the outputs must also meet `tol` against a float64 run of the oracle (every f32 tensor held as float64 at twice its
-        offset, as plan_harness.make_bases(wide=True) lays out a plan), so that an error the f32 oracle shares cannot hide.
-        Returns {output: (error against the f32 oracle, error against float64 or None)}."""
+    def execute(self, packed, ref64=False, oracle=True, want_variant=None, kind=""):
+        """Run packed records on the GPU over this case's arena and (oracle=True) through ops_ref on the same bytes, with ref64 also
+        in float64.  Returns the byte images (GPU result, f32 oracle or None, float64 oracle or None); read() takes a tensor out of one."""
         from s2lc_amd import _lib
 
-        prog = Program()
-        for k, f in pre:
-            prog.add(k, **f)
-        prog.add(kind, **fields)
-        packed = prog.pack()
         cpu = torch.zeros(self.arena.top + 256, dtype=torch.uint8)
         for name, (ref, data) in self.items.items():
             cpu[ref.off:ref.off + ref.nbytes] = data.contiguous().reshape(-1).view(torch.uint8)
@@ -99,6 +87,8 @@ class Case:
             _, var = _lib.profile_variants(packed, _lib.Bases().set("WS", cpu.cuda()), torch.cuda.current_stream().cuda_stream)
             assert int(var[-1]) == want_variant, f"{kind}: kernel family {int(var[-1])}, expected {want_variant}"
         got = gpu.cpu()
+        if not oracle:
+            return got, None, None
         wide = None
         if ref64:       # (from the inputs as written: the f32 oracle below overwrites `cpu` in place)
             wide = torch.zeros(2 * cpu.numel(), dtype=torch.uint8)
@@ -108,11 +98,36 @@ class Case:
                 wide[2 * ref.off:2 * ref.off + b.numel()] = b
             ops_ref.run_program(packed, {WS: wide}, D, wide=True)
         ops_ref.run_program(packed, {WS: cpu}, D)
+        return got, cpu, wide
+
+    def read(self, image, name, wide=False):
+        """tensor `name` out of a byte image of the arena (wide=True: the float64 layout, f32 held as f64 and bf16 as f32 at twice the offset)"""
+        ref, _ = self.items[name]
+        if not wide:
+            return image[ref.off:ref.off + ref.nbytes].view(_DT[ref.dtype]).reshape(ref.shape)
+        wdt = {"f32": torch.float64, "bf16": torch.float32}.get(ref.dtype, _DT[ref.dtype])
+        return image[2 * ref.off:2 * ref.off + ref.numel * wdt.itemsize].view(wdt).reshape(ref.shape)
+
+    def run(self, kind, outputs, tol=1e-4, sum0=(), pre=(), want_variant=None, per_column=(), ref64=False, **fields):
+        """sum0: outputs compared after summing their leading (statistics-replica) dimension.
+        pre: stage records to run first (e.g. WEIGHT_PACK).  want_variant: the kernel family the stage must have taken
+        (s2k_program_profile_variants, include/s2k.h: 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads,
+        5 f32-split; depthwise: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop).
+        per_column: outputs whose every last-dim column must also meet `tol` against that column's own max |ref| (a wrong
+        column among larger ones - e.g. a ragged last channel tile - hides under the whole tensor's max).
+        ref64: the outputs must also meet `tol` against a float64 run of the oracle (every f32 tensor held as float64 at twice its
+        offset, as plan_harness.make_bases(wide=True) lays out a plan), so that an error the f32 oracle shares cannot hide.
+        Returns {output: (error against the f32 oracle, error against float64 or None)}."""
+        prog = Program()
+        for k, f in pre:
+            prog.add(k, **f)
+        prog.add(kind, **fields)
+        got, cpu, wide = self.execute(prog.pack(), ref64=ref64, want_variant=want_variant, kind=kind)
         errs = {}
         for name in outputs:
             ref, _ = self.items[name]
-            a = got[ref.off:ref.off + ref.nbytes].view(_DT[ref.dtype]).double()
-            b = cpu[ref.off:ref.off + ref.nbytes].view(_DT[ref.dtype]).double()
+            a = self.read(got, name).reshape(-1).double()
+            b = self.read(cpu, name).reshape(-1).double()
             if name in sum0:
                 a, b = a.view(ref.shape).sum(0), b.view(ref.shape).sum(0)
             assert torch.isfinite(b).all(), f"{kind}:{name}: oracle produced non-finite values"
@@ -122,8 +137,7 @@ class Case:
             assert err < tol, f"{kind}:{name}: rel err {err:.3e} (max |ref| {denom:.3e})"
             err64 = None
             if wide is not None:
-                wdt = {"f32": torch.float64, "bf16": torch.float32}.get(ref.dtype, _DT[ref.dtype])
-                t = wide[2 * ref.off:2 * ref.off + ref.numel * wdt.itemsize].view(wdt).double()
+                t = self.read(wide, name, wide=True).reshape(-1).double()
                 if name in sum0:
                     t = t.view(ref.shape).sum(0)
                 assert torch.isfinite(t).all(), f"{kind}:{name}: float64 oracle produced non-finite values"
