@@ -87,6 +87,8 @@ int s2k_program_profile_ops(const S2kOp* ops, int begin, int end, void* const* b
  * Depthwise stages (DWCONV_FWD / _DGRAD / _WGRAD): 0 for the band kernels (dwconv_fwd_kernel, dwconv_dgrad_s1_kernel,
  * dwconv_dgrad_s2_kernel, dwconv_wgrad_kernel), 6 for the wave-per-channel plane kernels (dwconv_{fwd,dgrad,wgrad}_plane_kernel,
  * dwconv_{fwd,dgrad}_plane_s2_kernel), 7 for dwconv_wgrad_kernel walking images inside the workgroup (its image loop).
+ * ViT stages: CHAN_LN_FWD 0 for the tile kernel (chan_ln_fwd_kernel), 8 for the row kernel (chan_ln_fwd_rows_kernel);
+ * MAE_LOSS_FWD / _BWD 0 for the float4 form of mae_loss_rows_kernel (<*, true>), 9 for its scalar form (<*, false>).
  * bench.py uses it to attribute time and algorithmic FLOPs to the kernel names a rocprofv3 trace shows. */
 int s2k_program_profile_variants(const S2kOp* ops, int begin, int end, void* const* bases, int n_bases, void* stream,
                                  float* ms_per_op, int* variant_per_op);

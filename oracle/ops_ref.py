@@ -582,6 +582,11 @@ def op_attn_bwd(m: Mem, o):
     dst[:, 0, ..., :L].copy_(dq.permute(0, 1, 3, 2))
     dst[:, 1, ..., :L].copy_(dk.permute(0, 1, 3, 2))
     dst[:, 2, ..., :L].copy_(dv.permute(0, 1, 3, 2))
+    if o.get("DELTA", -1) >= 0 and o.get("O", -1) >= 0:      # delta[b][h][i] = sum_d dO[d][i] O[d][i] of the O handed in; row padding := 0
+        out = m.view(o["O"], (B, H, HD, LS))[..., :L].permute(0, 1, 3, 2)
+        delta = m.view(o["DELTA"], (B, H, LS))
+        delta.zero_()
+        delta[..., :L].copy_((do * out).sum(-1))
 
 
 def op_mae_mask_index(m: Mem, o):

@@ -129,7 +129,8 @@ def profile_ops(packed: np.ndarray, bases: Bases, stream: int) -> np.ndarray:
 def profile_variants(packed: np.ndarray, bases: Bases, stream: int):
     """(ms per stage, variant per stage): the kernel family each stage's launcher picked (include/s2k.h,
     s2k_program_profile_variants): 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads, 5 f32-split;
-    depthwise stages: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop."""
+    depthwise stages: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop; ViT stages: 8 the
+    LayerNorm row kernel (0 its tile kernel), 9 the scalar MAE-loss kernel (0 its float4 form)."""
     ms = np.zeros(len(packed), dtype=np.float32)
     var = np.zeros(len(packed), dtype=np.int32)
     with _guard(bases):

@@ -279,7 +279,8 @@ inline int tune_int(const char* name, int dflt) {
 // Which kernel family a stage's launcher picked (read by s2k_program_profile_variants): 0 = the stage's generic kernel,
 // 1 = the producer/consumer kernel (conv_pc_kernel / wgrad_pc_kernel), 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads, 5 f32-split;
 // depthwise stages: 0 = the band kernels, 6 = the wave-per-channel plane kernels (dwconv_*_plane_kernel, dwconv_*_plane_s2_kernel),
-// 7 = dwconv_wgrad_kernel's image loop (bloop > 0).  The full list is in include/s2k.h.
+// 7 = dwconv_wgrad_kernel's image loop (bloop > 0); ViT stages: 8 = chan_ln_fwd_rows_kernel (0 = the tile kernel), 9 = the scalar
+// form of mae_loss_rows_kernel (0 = its float4 form).  The full list is in include/s2k.h.
 extern thread_local int g_s2k_variant;
 
 // hipFuncSetAttribute acts on the current device: run a kernel's attribute call once per device.  std::call_once makes every

@@ -263,6 +263,7 @@ int launch_chan_ln_fwd(const S2kOp& op, const Ctx& c) {
     if (ln_rows_geometry(p, {p.x, p.y, p.mr})) {
         const unsigned grid = 8u * (unsigned)(p.pgroups * p.csplit) * (unsigned)cdiv(p.B, 8);
         hipLaunchKernelGGL(chan_ln_fwd_rows_kernel, dim3(grid), dim3(64 * LNR_NW), 0, c.stream, p);
+        g_s2k_variant = 8;
         return S2K_OK;
     }
     p.tiles_per_b = cdiv(p.HW, 64);
@@ -889,7 +890,7 @@ int launch_mae_loss_fwd(const S2kOp& op, const Ctx& c) {
     (void)hipMemsetAsync(p.acc, 0, 2 * sizeof(double), c.stream);
     const dim3 grid((unsigned)cdiv(p.LP, 256), (unsigned)(p.TUB * p.P), (unsigned)p.B);
     if (mae_vec(p)) hipLaunchKernelGGL((mae_loss_rows_kernel<false, true>), grid, dim3(256), 0, c.stream, p);
-    else hipLaunchKernelGGL((mae_loss_rows_kernel<false, false>), grid, dim3(256), 0, c.stream, p);
+    else { hipLaunchKernelGGL((mae_loss_rows_kernel<false, false>), grid, dim3(256), 0, c.stream, p); g_s2k_variant = 9; }
     hipLaunchKernelGGL(mae_loss_finish_kernel, dim3(1), dim3(64), 0, c.stream, p);
     return S2K_OK;
 }
@@ -907,7 +908,7 @@ int launch_mae_loss_bwd(const S2kOp& op, const Ctx& c) {
     if (!p.pred || !p.x || !p.mask || !p.acc || !p.dpred) { set_error("mae_loss_bwd: missing tensor"); return S2K_EINVAL; }
     const dim3 grid((unsigned)cdiv(p.LP, 256), (unsigned)(p.TUB * p.P), (unsigned)p.B);
     if (mae_vec(p)) hipLaunchKernelGGL((mae_loss_rows_kernel<true, true>), grid, dim3(256), 0, c.stream, p);
-    else hipLaunchKernelGGL((mae_loss_rows_kernel<true, false>), grid, dim3(256), 0, c.stream, p);
+    else { hipLaunchKernelGGL((mae_loss_rows_kernel<true, false>), grid, dim3(256), 0, c.stream, p); g_s2k_variant = 9; }
     return S2K_OK;
 }
 

@@ -85,7 +85,10 @@ class Case:
         torch.cuda.synchronize()
         if want_variant is not None:       # on a second copy of the inputs (a profiled run executes the stages again)
             _, var = _lib.profile_variants(packed, _lib.Bases().set("WS", cpu.cuda()), torch.cuda.current_stream().cuda_stream)
-            assert int(var[-1]) == want_variant, f"{kind}: kernel family {int(var[-1])}, expected {want_variant}"
+            if isinstance(want_variant, (list, tuple)):      # one family per record
+                assert [int(v) for v in var] == list(want_variant), f"{kind}: kernel families {[int(v) for v in var]}, expected {list(want_variant)}"
+            else:
+                assert int(var[-1]) == want_variant, f"{kind}: kernel family {int(var[-1])}, expected {want_variant}"
         got = gpu.cpu()
         if not oracle:
             return got, None, None
@@ -112,7 +115,8 @@ class Case:
         """sum0: outputs compared after summing their leading (statistics-replica) dimension.
         pre: stage records to run first (e.g. WEIGHT_PACK).  want_variant: the kernel family the stage must have taken
         (s2k_program_profile_variants, include/s2k.h: 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads,
-        5 f32-split; depthwise: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop).
+        5 f32-split; depthwise: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop; ViT stages:
+        CHAN_LN_FWD 0 tile kernel, 8 row kernel; MAE_LOSS_FWD / _BWD 0 float4 kernel, 9 scalar kernel).
         per_column: outputs whose every last-dim column must also meet `tol` against that column's own max |ref| (a wrong
         column among larger ones - e.g. a ragged last channel tile - hides under the whole tensor's max).
         ref64: the outputs must also meet `tol` against a float64 run of the oracle (every f32 tensor held as float64 at twice its

@@ -14,24 +14,27 @@ from tests.test_ops_gpu import Case
 pytestmark = pytest.mark.gpu
 
 
-# forward: HW % 4 == 0, HW <= 64, C >= 64 and B < 128 run the row kernel (a sample shared by channel splits), the rest the tile kernel
-LN_ROW_SHAPES = [(3, 768, 52), (2, 512, 200), (9, 130, 36), (17, 64, 32), (1, 1000, 1024), (2, 96, 196), (64, 768, 52)]
+# (B, C, HW, kernel family of the forward: tests/vit_dispatch.py).  The forward takes the row kernel (8: a sample shared by channel
+# splits) only for HW % 4 == 0, 32 <= HW <= 64, C >= 64, B < 128 and 16-byte-aligned tensors; (2, 512, 200), (1, 1000, 1024) and
+# (2, 96, 196) have longer rows and run the tile kernel (0), as every backward does.
+LN_SHAPES = [(3, 768, 52, 8), (2, 512, 200, 0), (9, 130, 36, 8), (17, 64, 32, 8), (1, 1000, 1024, 0), (2, 96, 196, 0), (64, 768, 52, 8)]
+LN_FWD = [(2, 32, 50, 1e-5, 0), (2, 768, 197, 1e-5, 0), (1, 96, 28 * 28, 1e-6, 0), (3, 16, 64, 1e-6, 0), (1, 5, 3, 1e-5, 0)] \
+    + [(*s[:3], 1e-6, s[3]) for s in LN_SHAPES]
 
 
-@pytest.mark.parametrize("B,C,HW,eps", [(2, 32, 50, 1e-5), (2, 768, 197, 1e-5), (1, 96, 28 * 28, 1e-6), (3, 16, 64, 1e-6), (1, 5, 3, 1e-5)]
-                         + [(*s, 1e-6) for s in LN_ROW_SHAPES])
-def test_chan_ln_fwd(B, C, HW, eps):
+@pytest.mark.parametrize("B,C,HW,eps,want", LN_FWD, ids=[f"{r[0]}-{r[1]}-{r[2]}-{r[3]}" for r in LN_FWD])
+def test_chan_ln_fwd(B, C, HW, eps, want):
     c = Case(1)
     x = c.t("x", (B, C, HW), scale=2.0)
     g, b = c.t("gamma", (C,), "pos"), c.t("beta", (C,))
     y, mr = c.t("y", (B, C, HW), "nan"), c.t("mr", (B, HW, 2), "nan")
-    c.run("CHAN_LN_FWD", ["y", "mr"], tol=2e-5, X=x, GAMMA=g, BETA=b, Y=y, MR=mr, B=B, C=C, HW=HW, EPS=eps)
+    c.run("CHAN_LN_FWD", ["y", "mr"], tol=2e-5, want_variant=want, ref64=True, X=x, GAMMA=g, BETA=b, Y=y, MR=mr, B=B, C=C, HW=HW, EPS=eps)
 
 
 @pytest.mark.parametrize("B,C,HW,accum,params,extra", [(2, 32, 50, 0, True, ""), (2, 768, 197, 1, True, ""), (1, 96, 28 * 28, 1, False, ""),
                                                        (3, 16, 64, 0, True, ""), (1, 5, 3, 0, True, ""), (5, 100, 52, 1, True, ""),
                                                        (2, 768, 197, 1, True, "dxin+dsum"), (3, 40, 50, 0, False, "dsum")]
-                         + [(*s, i % 2, i % 3 != 0, ["", "dxin", "dsum", "dxin+dsum"][i % 4]) for i, s in enumerate(LN_ROW_SHAPES)])
+                         + [(*s[:3], i % 2, i % 3 != 0, ["", "dxin", "dsum", "dxin+dsum"][i % 4]) for i, s in enumerate(LN_SHAPES)])
 def test_chan_ln_bwd(B, C, HW, accum, params, extra):
     c = Case(2)
     xd = torch.randn(B, C, HW, generator=c.gen) * 2
@@ -46,7 +49,8 @@ def test_chan_ln_bwd(B, C, HW, accum, params, extra):
     db = c.t("dbeta", (C,), "randn") if params else None
     dxin = c.t("dxin", (B, C, HW), "randn") if "dxin" in extra else None     # out-of-place accumulate: DX = DXIN + ...
     dsum = c.t("dsum", (C,), "randn") if "dsum" in extra else None           # DSUM[c] += sum of the new DX values
-    c.run("CHAN_LN_BWD", ["dx"] + (["dgamma", "dbeta"] if params else []) + (["dsum"] if dsum is not None else []), tol=1e-4, DY=dy, X=x, MR=mr,
+    c.run("CHAN_LN_BWD", ["dx"] + (["dgamma", "dbeta"] if params else []) + (["dsum"] if dsum is not None else []), tol=1e-4, ref64=True, DY=dy, X=x,
+          MR=mr,
           GAMMA=g, DX=dx, DGAMMA=dg, DBETA=db, DXIN=dxin, DSUM=dsum, B=B, C=C, HW=HW, ACCUM=1 if dxin is not None else accum)
 
 
@@ -119,7 +123,12 @@ def test_convt_wgrad_with_gelu_operand():
 # (B, heads, head dim, tokens, row stride; 0 = tokens)
 ATTN = [(2, 2, 16, 17, 0), (2, 2, 8, 50, 0), (1, 3, 64, 197, 0), (1, 2, 32, 197, 0), (2, 2, 64, 50, 0), (1, 1, 64, 224, 0), (1, 2, 32, 33, 0),
         (1, 1, 5, 3, 0), (2, 2, 32, 50, 52), (1, 2, 64, 197, 200), (1, 2, 32, 197, 200), (2, 2, 16, 17, 20), (1, 1, 32, 300, 0),
-        (1, 2, 64, 260, 264), (1, 1, 7, 1, 4), (1, 2, 64, 589, 592)]   # 589 = 3 frames x 196 patches + cls
+        (1, 2, 64, 260, 264), (1, 1, 7, 1, 4), (1, 2, 64, 589, 592),   # 589 = 3 frames x 196 patches + cls
+        # head dims 33..63 on the two-tile kernels at more than one token tile (the clamped rows d >= HD staged into LDS must be
+        # cancelled by the zeroed held operand), odd head dims on the one-tile kernels at more than one tile
+        (2, 3, 33, 70, 72), (1, 2, 40, 129, 132), (2, 1, 48, 197, 200), (1, 2, 63, 65, 0), (3, 2, 17, 70, 0), (1, 2, 24, 33, 36),
+        # one token short of a tile, whole tiles, exactly one 4-wave group, one group + a lone active wave beside three idle ones
+        (2, 2, 64, 31, 32), (1, 2, 64, 32, 0), (1, 2, 64, 64, 0), (1, 2, 64, 128, 0), (1, 2, 64, 129, 132)]
 
 
 def _attn_reference(qkv, B, H, HD, L, scale):
@@ -135,7 +144,7 @@ def test_attn_fwd(B, H, HD, L, LS):
     qkv = c.t("qkv", (B, 3 * H * HD, S))
     o = c.t("o", (B, H * HD, S), "nan")
     lse = c.t("lse", (B, H, S), "nan")
-    c.run("ATTN_FWD", ["o", "lse"], tol=1e-4, QKV=qkv, O=o, LSE=lse, B=B, HEADS=H, HD=HD, L=L, LS=LS, SCALE=HD ** -0.5)
+    c.run("ATTN_FWD", ["o", "lse"], tol=1e-4, ref64=True, QKV=qkv, O=o, LSE=lse, B=B, HEADS=H, HD=HD, L=L, LS=LS, SCALE=HD ** -0.5)
 
 
 @pytest.mark.parametrize("B,H,HD,L,LS", ATTN)
@@ -153,7 +162,7 @@ def test_attn_bwd(B, H, HD, L, LS):
     do = c.t("do", (B, H * HD, S))
     dqkv = c.t("dqkv", (B, 3 * H * HD, S), "nan")
     delta = c.t("delta", (B, H, S), "nan")
-    c.run("ATTN_BWD", ["dqkv"], tol=2e-4, QKV=qkv, DO=do, DQKV=dqkv, O=o, LSE=lse, DELTA=delta, B=B, HEADS=H, HD=HD, L=L, LS=LS,
+    c.run("ATTN_BWD", ["dqkv"], tol=2e-4, ref64=True, QKV=qkv, DO=do, DQKV=dqkv, O=o, LSE=lse, DELTA=delta, B=B, HEADS=H, HD=HD, L=L, LS=LS,
           SCALE=HD ** -0.5)
 
 
@@ -213,8 +222,13 @@ def test_patchify(B, C, T, H, P, TUB):
     c.run("PATCHIFY", ["out"], tol=1e-30, X=x, OUT=out, B=B, C=C, T=T, H=H, W=H, P=P, TUB=TUB)
 
 
-@pytest.mark.parametrize("B,C,T,H,P,TUB,norm_pix", [(2, 3, 1, 32, 8, 1, 0), (2, 3, 3, 32, 8, 1, 1), (1, 6, 1, 224, 16, 1, 0), (1, 2, 4, 16, 4, 2, 1)])
+MAE_LOSS = [(2, 3, 1, 32, 8, 1, 0), (2, 3, 3, 32, 8, 1, 1), (1, 6, 1, 224, 16, 1, 0), (1, 2, 4, 16, 4, 2, 1)]      # (B, C, T, H, P, TUB, NORM_PIX)
+
+
+@pytest.mark.parametrize("B,C,T,H,P,TUB,norm_pix", MAE_LOSS)
 def test_mae_loss_fwd_bwd(B, C, T, H, P, TUB, norm_pix):
+    """every case here has P % 4 == 0, W % 4 == 0 and aligned images: the float4 kernel (family 0); the scalar kernel and the
+    options the plans use are in tests/test_vit_kernels_gpu.py"""
     c = Case(13)
     L = (T // TUB) * (H // P) ** 2
     PD = TUB * P * P * C
@@ -225,7 +239,7 @@ def test_mae_loss_fwd_bwd(B, C, T, H, P, TUB, norm_pix):
     loss = c.t("loss", (1,), "nan")
     acc = c.t("acc", (2,), "zeros", "f64")
     geo = dict(B=B, C=C, T=T, H=H, W=H, P=P, TUB=TUB, LP=LP, L_OFF=1, NORM_PIX=norm_pix)
-    c.run("MAE_LOSS_FWD", ["loss", "acc"], tol=2e-5, PRED=pred, IMGS=x, MASK=mask, LOSS=loss, ACC=acc, **geo)
+    c.run("MAE_LOSS_FWD", ["loss", "acc"], tol=2e-5, want_variant=0, PRED=pred, IMGS=x, MASK=mask, LOSS=loss, ACC=acc, **geo)
     # backward reads ACC[1] (the mask count) as the forward left it
     c2 = Case(13)
     pred = c2.t("pred", (B, PD, LP))
@@ -235,7 +249,7 @@ def test_mae_loss_fwd_bwd(B, C, T, H, P, TUB, norm_pix):
     acc = c2.t("acc", (2,), torch.tensor([0.0, mk.sum().item()]), "f64")
     gout = c2.t("gout", (1,), torch.tensor([0.7]))
     dpred = c2.t("dpred", (B, PD, LP), "nan")
-    c2.run("MAE_LOSS_BWD", ["dpred"], tol=2e-5, PRED=pred, IMGS=x, MASK=mask, ACC=acc, GOUT=gout, DPRED=dpred, **geo)
+    c2.run("MAE_LOSS_BWD", ["dpred"], tol=2e-5, want_variant=0, PRED=pred, IMGS=x, MASK=mask, ACC=acc, GOUT=gout, DPRED=dpred, **geo)
 
 
 @pytest.mark.parametrize("B,C,L,off,Lout", [(2, 48, 17, 1, 16), (3, 1536, 197, 1, 196), (2, 768, 50, 0, 50), (1, 5, 3, 0, 3)])
