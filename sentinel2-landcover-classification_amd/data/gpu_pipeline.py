@@ -13,6 +13,12 @@ the reference's largest area) are uploaded once and stay resident in HBM; every 
 Randomness: albumentations draws from Python's `random`; here crop offsets and flips are drawn from a `torch.Generator`
 on the host with the same formulas (`int((H - S + 1) * u)`, `u < p`) and passed to the stage, like every other random
 draw of this library (drop-connect, MAE masking).  Given the same draws the output is bit-identical to the reference's.
+
+Dataset statistics: the three passes the reference makes over the whole dataset on the CPU before a run starts read only what is
+resident here, so each is one streaming read on the GPU (stages TILE_MOMENTS / TILE_LABEL_HIST, host derivations in
+data/dataset_stats.py): `band_mean_std` (calculate_mean_std -> the `mean`, `std` of this class), `class_probabilities`
+(get_class_probabilities -> `EfficientNetConfig.class_distribution`, `losses.get_loss`) and `sample_weights` + `weighted_indices`
+(get_sample_weights + WeightedRandomSampler -> the tile indices given to `draw_params`).
 """
 from __future__ import annotations
 
@@ -23,6 +29,7 @@ import torch
 
 from .. import _lib
 from ..plan import opdefs as D
+from . import dataset_stats as DS
 from ..plan.program import Program, TRef
 
 # CNES land-cover classes 1..23 grouped as in src/configs/cnes_labell_mappings.py:47-75 (class 0 = outside France)
@@ -133,3 +140,107 @@ class GpuTilePipeline:
         if not self.squeeze and self.frames == 1:
             x = x.unsqueeze(2)            # per sample (c, 1, h, w), s2osm_dataset.py:64-66
         return S2OSMSample(x=x, y=y)
+
+    # ---- dataset statistics over the resident tiles (data/dataset_stats.py) --------------------------------------------------
+    def _stats_index(self, indices, need_labels: bool, limit: int | None = None) -> torch.Tensor:
+        """int32 [M] tile indices (None = all resident tiles), validated on the host: the stages do not range-check them.
+        Argument errors come first (ValueError), then the refusal to run anywhere but on the GPU."""
+        if self.raw is None:
+            raise RuntimeError("call load() first")
+        if need_labels and self.labels is None:
+            raise ValueError("the pipeline was loaded without labels")
+        N = self.raw.shape[0]
+        idx = torch.arange(N, dtype=torch.int64) if indices is None else torch.as_tensor(indices, dtype=torch.int64).reshape(-1).cpu()
+        if idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= N:
+            raise ValueError("tile indices out of range (or none given)")
+        if limit is not None and idx.numel() > limit:
+            raise ValueError(f"at most {limit} tiles per call (the exact-integer bound of TILE_MOMENTS)")
+        if not self.raw.is_cuda:
+            raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
+        return idx.to(torch.int32)
+
+    def _window(self, window) -> tuple[int, int, int, int]:
+        H, W = self.raw.shape[2:]
+        if isinstance(window, str):
+            if window == "tile":
+                return 0, 0, H, W
+            if window == "center":                  # get_center_crop_coords, as draw_params(training=False)
+                return (H - self.S) // 2, (W - self.S) // 2, self.S, self.S
+            raise ValueError("window must be 'tile', 'center' or (y0, x0, h, w)")
+        y0, x0, h, w = (int(v) for v in window)
+        if y0 < 0 or x0 < 0 or h <= 0 or w <= 0 or y0 + h > H or x0 + w > W:
+            raise ValueError("window outside the tile")
+        return y0, x0, h, w
+
+    @torch.no_grad()
+    def _moments(self, indices=None):
+        """(SUMS int64 [C, 2], SDPART float64 [C, NB], M, H*W) of one TILE_MOMENTS stage over the selected tiles, on the device."""
+        idx = self._stats_index(indices, need_labels=False, limit=DS.MAX_MOMENT_TILES)
+        M = idx.numel()
+        N, C, H, W = self.raw.shape
+        NB = D.moments_blocks(H * W)
+        idx_d = idx.to(self.device)
+        sums = torch.zeros(C, 2, dtype=torch.int64, device=self.device)
+        sdpart = torch.zeros(C, NB, dtype=torch.float64, device=self.device)
+        prog = Program()
+        prog.add("TILE_MOMENTS", RAW=TRef(D.BASE["X"], 0, (N, C, H, W), "i16"), INDEX=TRef(D.BASE["AUX"], 0, (M,), "i32"),
+                 SUMS=TRef(D.BASE["OUT"], 0, (C, 2), "i64"), SDPART=TRef(D.BASE["DOUT"], 0, (C, NB), "f64"),
+                 M=M, C=C, H=H, W=W, NSRC=N, NB=NB)
+        bases = _lib.Bases().set("X", self.raw).set("AUX", idx_d).set("OUT", sums).set("DOUT", sdpart)
+        _lib.run(prog.pack(), bases, torch.cuda.current_stream(self.device).cuda_stream)
+        return sums, sdpart, M, H * W
+
+    def band_mean_std(self, indices=None, pooled: bool = False):
+        """(mean, std) float32 CPU tensors [C] over the selected raw tiles - the two tensors the reference's `calculate_mean_std`
+        stores in mean_std.pt, ready for `GpuTilePipeline(mean, std)`.  `std` is the reference's statistic, the mean over pixel
+        positions of the per-position standard deviation across tiles; pooled=True returns the standard deviation over all values
+        of the band instead (dataset_stats.mean_std_from_moments)."""
+        sums, sdpart, M, HW = self._moments(indices)
+        mean, std, pooled_std = DS.mean_std_from_moments(sums.cpu(), sdpart.cpu(), M, HW)
+        return mean, (pooled_std if pooled else std)
+
+    @torch.no_grad()
+    def label_histogram(self, num_classes: int, indices=None, window="tile") -> torch.Tensor:
+        """int64 [M, num_classes] on the device: per selected tile, how often each class (after the label map's remap) occurs in
+        the window - "tile", "center" (the S x S centre crop: what `dataset[i]` yields under the reference's deterministic
+        transform) or (y0, x0, h, w).  Remapped labels outside [0, num_classes) are not counted."""
+        idx = self._stats_index(indices, need_labels=True)
+        K, M = int(num_classes), idx.numel()
+        if not 1 <= K <= 256:
+            raise ValueError("num_classes must be in 1..256")
+        y0, x0, wh, ww = self._window(window)
+        N, H, W = self.labels.shape
+        idx_d = idx.to(self.device)
+        hist = torch.zeros(M, K, dtype=torch.int64, device=self.device)
+        prog = Program()
+        prog.add("TILE_LABEL_HIST", LABELS=TRef(D.BASE["Y"], 0, (N, H, W), "u8"), INDEX=TRef(D.BASE["AUX"], 0, (M,), "i32"),
+                 LUT=TRef(D.BASE["NOISE"], 0, (256,), "i32"), HIST=TRef(D.BASE["OUT"], 0, (M, K), "i64"),
+                 M=M, H=H, W=W, K=K, Y0=y0, X0=x0, WH=wh, WW=ww, NSRC=N)
+        bases = _lib.Bases().set("Y", self.labels).set("AUX", idx_d).set("NOISE", self.lut).set("OUT", hist)
+        _lib.run(prog.pack(), bases, torch.cuda.current_stream(self.device).cuda_stream)
+        return hist
+
+    def class_probabilities(self, num_classes: int, ignore_zero_label: bool, indices=None, max_tiles: int = 2500,
+                            generator: torch.Generator | None = None) -> torch.Tensor:
+        """float32 CPU tensor [num_classes]: the reference's `get_class_probabilities` over whole tiles (it runs on the dataset
+        before any crop transform is attached).  Like its `random.sample`, a subset of max_tiles tiles is drawn on the host
+        (without replacement, from `generator`) when more are selected."""
+        idx = self._stats_index(indices, need_labels=True)
+        if idx.numel() > max_tiles:
+            idx = idx[torch.randperm(idx.numel(), generator=generator)[:max_tiles]]
+        return DS.probabilities_from_hist(self.label_histogram(num_classes, idx, "tile").cpu(), ignore_zero_label)
+
+    def sample_weights(self, class_distribution, ignore_zero_label: bool = False, indices=None, window="center") -> torch.Tensor:
+        """float32 CPU tensor [M]: the reference's `get_sample_weights` for the selected tiles, in their order."""
+        K = len(torch.as_tensor(class_distribution).reshape(-1))
+        return DS.sample_weights_from_hist(self.label_histogram(K, indices, window).cpu(), class_distribution, ignore_zero_label)
+
+    def weighted_indices(self, weights, num_samples: int, generator: torch.Generator | None = None) -> torch.Tensor:
+        """int64 [num_samples] positions drawn with replacement in proportion to `weights`, on the host: exactly what
+        `WeightedRandomSampler(weights, num_samples, True, generator=generator)` yields.  They index the tiles the weights were
+        computed for (`indices[drawn]` for a subset) and go straight into `draw_params`."""
+        if self.raw is None:
+            raise RuntimeError("call load() first")
+        if not self.raw.is_cuda:
+            raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
+        return DS.weighted_indices(weights, num_samples, generator)

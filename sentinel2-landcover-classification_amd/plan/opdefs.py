@@ -244,6 +244,20 @@ OPS: dict[str, tuple[list[str], list[str], list[str], list[str]]] = {
     # over C*KH*KW pseudo-channels - the parameter's own [M][C][KH][KW] layout is that 1x1 weight - on the fast pixel-tile kernels
     # instead of the generic strided path (17 - 24 TF/s there; the weight gradient was the last, fully exposed stage of a step)
     "IM2COL": (["X", "Y"], [], ["B", "C", "H", "W", "KH", "KW", "STRIDE", "PAD_T", "PAD_L", "HO", "WO"], []),
+    # dataset statistics over the resident tiles of the input pipeline (data/gpu_pipeline.py; the reference's get_class_probabilities /
+    # get_sample_weights, src/utils.py:152-217): per selected tile m, the class histogram of a window of its label raster
+    #   HIST[m][k] += #{(i, j) in [Y0, Y0 + WH) x [X0, X0 + WW) : LUT[LABELS[INDEX[m]][i][j]] == k}      (int64 [M][K], 1 <= K <= 256)
+    # LUT values outside [0, K) are skipped (as CONFUSION skips labels).  The stage accumulates: the caller zeroes HIST.  LABELS uint8
+    # [NSRC][H][W], INDEX int32 [M] (any order, duplicates allowed; validated on the host before upload, like TILE_PREP's PARAMS)
+    "TILE_LABEL_HIST": (["LABELS", "INDEX", "LUT", "HIST"], [], ["M", "H", "W", "K", "Y0", "X0", "WH", "WW", "NSRC"], []),
+    # per-band moments of the selected raw tiles (the reference's WelfordsMethod, src/data/calculate_dataset_statistics.py:20-43, which
+    # keeps one running mean / M2 PER PIXEL POSITION across samples and averages over positions at the end).  Per position (c, p),
+    # p < H*W:  s1 = sum_m x, s2 = sum_m x^2 over x = RAW[INDEX[m]][c][p] - exact integers for M <= 65535 (|s1| < 2^31, M*s2 < 2^63).
+    #   SUMS[c] += {sum_p s1, sum_p s2}      (int64 [C][2]; the second is to be read as UNSIGNED: it stays below 2^64 for M*H*W < 2^34)
+    #   SDPART[c][blk] = sum over the positions of block blk of sqrt((M*s2 - s1^2) / (M*(M - 1)))    (f64 [C][NB]; zeros for M == 1)
+    # with the numerator evaluated exactly in int64 and a fixed summation order: bit-identical run to run.  A block is 2048 consecutive
+    # positions: NB = ceil(H*W / 2048) (moments_blocks below).  The host adds the NB partials per band.
+    "TILE_MOMENTS": (["RAW", "INDEX", "SUMS", "SDPART"], [], ["M", "C", "H", "W", "NSRC", "NB"], []),
 }
 # Tensor slots a stage WRITES (everything else it only reads).  Used by the planner's side-stream hazard pass (unet_plan.finish_plan:
 # a main-stream stage that writes what an outstanding side-stream stage still reads must wait for the side stream first); a kind
@@ -260,10 +274,18 @@ WRITES: dict[str, tuple[str, ...]] = {
     "IDS_TO_DEC_IDX": ("DEC_IDX",), "TOKEN_GATHER": ("OUT",), "TOKEN_SCATTER": ("DIN", "DFILL"), "PATCHIFY": ("X", "OUT"),
     "MAE_LOSS_FWD": ("LOSS", "ACC"), "MAE_LOSS_BWD": ("DPRED",), "TRANSPOSE_CL": ("Y",), "CONFUSION": ("HIST",), "DROP_GATE": ("GATE",),
     "TILE_PREP": ("X", "Y"), "SE_BN_SUMS": ("DGATE", "PS"), "SE_BN_COMBINE": ("STATS2",), "SPACE_TO_DEPTH": ("Y",), "UPSAMPLE_ZERO": ("Y",),
-    "SE_FC_WGRAD": ("DW1", "DB1", "DW2", "DB2"), "IM2COL": ("Y",),
+    "SE_FC_WGRAD": ("DW1", "DB1", "DW2", "DB2"), "IM2COL": ("Y",), "TILE_LABEL_HIST": ("HIST",), "TILE_MOMENTS": ("SUMS", "SDPART"),
 }
 for _k, _w in WRITES.items():
     assert _k in OPS and all(x in OPS[_k][0] for x in _w), _k
+
+MOMENTS_BLOCK = 2048      # pixel positions per workgroup of TILE_MOMENTS (256 threads x 8 positions)
+
+
+def moments_blocks(HW: int) -> int:
+    """NB of TILE_MOMENTS: workgroups (= SDPART slots) per band."""
+    return (HW + MOMENTS_BLOCK - 1) // MOMENTS_BLOCK
+
 
 KIND = {name: i + 1 for i, name in enumerate(OPS)}
 NAME_OF = {i: name for name, i in KIND.items()}
