@@ -258,6 +258,21 @@ OPS: dict[str, tuple[list[str], list[str], list[str], list[str]]] = {
     # with the numerator evaluated exactly in int64 and a fixed summation order: bit-identical run to run.  A block is 2048 consecutive
     # positions: NB = ceil(H*W / 2048) (moments_blocks below).  The host adds the NB partials per band.
     "TILE_MOMENTS": (["RAW", "INDEX", "SUMS", "SDPART"], [], ["M", "C", "H", "W", "NSRC", "NB"], []),
+    # whole-tile prediction (predict.py; csrc/predict.hip): blend the logits of overlapping S x S windows of M tiles into one [K][H][W]
+    # prediction per tile - a gather with a fixed summation order, no float atomics, bit-identical run to run.  LOGITS f32
+    # [M][F][NY][NX][K][S][S]: window (i, j) of tile slot m under flip variant f as the model returned it (still flipped); YS i32 [NY] /
+    # XS i32 [NX] window origins (ascending, unique, first 0, last H - S / W - S, gaps <= S: validated on the host before upload, like
+    # TILE_PREP's PARAMS); FLIPS i32 [F] (1 <= F <= 4, bit 0 horizontal, bit 1 vertical, TILE_PREP's meaning); W1 f32 [S] > 0.
+    # Per tile m and pixel (y, x): for f ascending, the i with YS[i] <= y < YS[i] + S ascending, the j likewise, with (a, b) =
+    # (y - YS[i], x - XS[j]) and v[k] the window's value at (a, b) mirrored in the axes FLIPS[f] names (MODE 1: the softmax over k of
+    # that window pixel; MODE 0: as is)
+    #   acc[k] += W1[a] * W1[b] * v[k],  ws += W1[a] * W1[b];   BLEND[m][k][y][x] = acc[k] / ws  (f32 [M][K][H][W], optional)
+    #   MASK[m][y][x] = first maximum over k of acc[k] / ws  (i64 [M][H][W], optional; ARGMAX's rule)
+    #   HIST[t][MASK] += 1 with t = LUT[LABELS[INDEX[m]][y][x]], skipped unless 0 <= t < K  (i64 [K][K], optional; accumulates - the
+    #   caller zeroes it; LABELS u8 [NSRC][H][W], INDEX i32 [M], LUT i32 [256]; counted in LDS per workgroup, 64-bit integer atomics)
+    # 1 <= K <= 32, LOGITS < 2^31 elements.
+    "WINDOW_BLEND": (["LOGITS", "YS", "XS", "FLIPS", "W1", "BLEND", "MASK", "LABELS", "INDEX", "LUT", "HIST"], [],
+                     ["M", "F", "NY", "NX", "K", "H", "W", "S", "NSRC", "MODE"], []),
 }
 # Tensor slots a stage WRITES (everything else it only reads).  Used by the planner's side-stream hazard pass (unet_plan.finish_plan:
 # a main-stream stage that writes what an outstanding side-stream stage still reads must wait for the side stream first); a kind
@@ -275,6 +290,7 @@ WRITES: dict[str, tuple[str, ...]] = {
     "MAE_LOSS_FWD": ("LOSS", "ACC"), "MAE_LOSS_BWD": ("DPRED",), "TRANSPOSE_CL": ("Y",), "CONFUSION": ("HIST",), "DROP_GATE": ("GATE",),
     "TILE_PREP": ("X", "Y"), "SE_BN_SUMS": ("DGATE", "PS"), "SE_BN_COMBINE": ("STATS2",), "SPACE_TO_DEPTH": ("Y",), "UPSAMPLE_ZERO": ("Y",),
     "SE_FC_WGRAD": ("DW1", "DB1", "DW2", "DB2"), "IM2COL": ("Y",), "TILE_LABEL_HIST": ("HIST",), "TILE_MOMENTS": ("SUMS", "SDPART"),
+    "WINDOW_BLEND": ("BLEND", "MASK", "HIST"),
 }
 for _k, _w in WRITES.items():
     assert _k in OPS and all(x in OPS[_k][0] for x in _w), _k

@@ -1,0 +1,193 @@
+"""Whole-tile prediction: sliding-window inference over the resident tiles of a `GpuTilePipeline`, blended on the GPU.
+
+The reference stops at per-crop logits (`predict_step`, src/train_segmentation.py:106; src/experiments/inference_demo.py), and its
+validation numbers come from the centre crop.  A land-cover user asks for the class map of a whole 512 x 512 Sentinel-2 tile; Prithvi
+has fixed position tables and only ever sees S x S = 224 x 224, so the tile is predicted as overlapping windows whose logits are
+combined.  Everything around that step exists already - TILE_PREP cuts windows from explicit {tile, y0, x0, flips} params in one
+launch, `metrics.SegMetrics` defines the metrics - and the step itself is one stage, WINDOW_BLEND (plan/opdefs.py, csrc/predict.hip):
+a gather with a fixed summation order, so a prediction is bit-identical from run to run and independent of `windows_per_batch`.
+
+    predictor = TilePredictor(model, pipe, num_classes=4)               # stride S // 2, Hann profile, softmax blended
+    class_map = predictor.predict([3, 17])                              # int64 [2, H, W] on the device
+    predictor.evaluate(metrics)                                         # whole-tile confusion counts into metrics.hist
+    metrics.compute()                                                   # whole-tile IoU / accuracy / F1
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import _lib
+from .plan import opdefs as D
+from .plan.program import Program, TRef
+
+MAX_CLASSES = 32                 # WINDOW_BLEND keeps a pixel quad's K sums in registers
+MAX_LOGITS = (1 << 31) - 1       # elements of one LOGITS buffer (the stage's bound)
+
+
+def window_origins(size: int, S: int, stride: int) -> list[int]:
+    """Origins of the S-wide windows that cover [0, size): 0, stride, 2 * stride, ... and a final size - S where the run does not end
+    there.  Ascending and unique; stride <= S, so consecutive windows leave no gap."""
+    size, S, stride = int(size), int(S), int(stride)
+    if S < 1 or S > size:
+        raise ValueError("the window must fit the tile (1 <= S <= size)")
+    if not 1 <= stride <= S:
+        raise ValueError("stride must be in 1..S (a larger one leaves pixels uncovered)")
+    out = list(range(0, size - S + 1, stride))
+    if out[-1] != size - S:
+        out.append(size - S)
+    return out
+
+
+def check_origins(origins, size: int, S: int) -> None:
+    """What WINDOW_BLEND assumes of YS / XS and does not check on the device: ascending, unique, first 0, last size - S, gaps <= S."""
+    o = [int(v) for v in origins]
+    if not o or o[0] != 0 or o[-1] != size - S or any(b <= a or b - a > S for a, b in zip(o[:-1], o[1:])):
+        raise ValueError("window origins must ascend from 0 to size - S in steps of 1..S")
+
+
+def window_profile(S: int, kind: str = "hann") -> torch.Tensor:
+    """float32 [S], strictly positive and symmetric: the 1-D blending profile; a window pixel (a, b) weighs profile[a] * profile[b].
+    "hann": sin^2(pi (i + 1/2) / S) - the half-sample shift keeps the ends above zero; "uniform": ones."""
+    S = int(S)
+    if S < 1:
+        raise ValueError("S must be positive")
+    if kind == "uniform":
+        return torch.ones(S, dtype=torch.float32)
+    if kind != "hann":
+        raise ValueError("window must be 'hann' or 'uniform'")
+    half = [math.sin(math.pi * (i + 0.5) / S) ** 2 for i in range((S + 1) // 2)]
+    return torch.tensor(half + half[:S // 2][::-1], dtype=torch.float64).to(torch.float32)      # mirrored: symmetric bit for bit
+
+
+class TilePredictor:
+    """model: any callable from the pipeline's batch `x` ([B, C, S, S], or [B, C, 1, S, S] unless the pipeline squeezes the time
+    dimension) to float32 logits [B, num_classes, S, S]; an `nn.Module` is run in eval mode.  blend="probs" averages the windows'
+    softmax, "logits" their raw values; `flips` are the test-time flip variants (bit 0 horizontal, bit 1 vertical), each window is
+    predicted under every one of them and un-flipped by the stage.  `tiles_per_launch` tiles share one LOGITS buffer and one
+    WINDOW_BLEND launch (default: as many as keep the buffer below 2 GiB, at most 8)."""
+
+    def __init__(self, model, pipeline, num_classes: int, stride: int | None = None, window: str = "hann", blend: str = "probs",
+                 flips=(0,), windows_per_batch: int = 32, tiles_per_launch: int | None = None):
+        self.model, self.pipe, self.K, self.S = model, pipeline, int(num_classes), int(pipeline.S)
+        self.stride = self.S // 2 if stride is None else int(stride)
+        self.flips = [int(f) for f in flips]
+        self.wpb = int(windows_per_batch)
+        self.tpl = None if tiles_per_launch is None else int(tiles_per_launch)
+        if not 1 <= self.K <= MAX_CLASSES:
+            raise ValueError(f"num_classes must be in 1..{MAX_CLASSES}")
+        if not 1 <= self.stride <= self.S:
+            raise ValueError("stride must be in 1..random_crop_size")
+        if blend not in ("probs", "logits"):
+            raise ValueError("blend must be 'probs' or 'logits'")
+        if not 1 <= len(self.flips) <= 4 or len(set(self.flips)) != len(self.flips) or any(not 0 <= f <= 3 for f in self.flips):
+            raise ValueError("flips: 1..4 different values out of 0..3")
+        if self.wpb < 1 or (self.tpl is not None and self.tpl < 1):
+            raise ValueError("windows_per_batch and tiles_per_launch must be positive")
+        self.mode = 1 if blend == "probs" else 0
+        self.profile = window_profile(self.S, window)
+
+    # ---- public surface ------------------------------------------------------------------------------------------------------
+    def predict(self, indices=None) -> torch.Tensor:
+        """int64 [M, H, W] on the device: the class of every pixel of the selected tiles (None = every resident tile)."""
+        return self._run(indices, want="mask")
+
+    def predict_blend(self, indices=None) -> torch.Tensor:
+        """float32 [M, K, H, W] on the device: the blended probabilities (blend="probs") or logits."""
+        return self._run(indices, want="blend")
+
+    def evaluate(self, metrics, indices=None) -> None:
+        """Add the whole-tile confusion counts of the selected tiles - hist[true][predicted] against the pipeline's resident labels
+        after its label map - into `metrics.hist` (a `metrics.SegMetrics`), inside the blending launch itself."""
+        if int(metrics.C) != self.K:
+            raise ValueError("metrics.num_classes differs from the predictor's")
+        self._run(indices, want="hist", metrics=metrics)
+
+    # ---- implementation ------------------------------------------------------------------------------------------------------
+    def _geometry(self):
+        H, W = (int(v) for v in self.pipe.raw.shape[2:])
+        ys, xs = window_origins(H, self.S, self.stride), window_origins(W, self.S, self.stride)
+        check_origins(ys, H, self.S)
+        check_origins(xs, W, self.S)
+        per_tile = len(self.flips) * len(ys) * len(xs) * self.K * self.S * self.S
+        if per_tile > MAX_LOGITS:
+            raise ValueError("one tile's window logits exceed 2^31 - 1 elements: raise the stride or drop flip variants")
+        tpl = max(1, min(8, MAX_LOGITS // per_tile)) if self.tpl is None else self.tpl
+        if tpl * per_tile > MAX_LOGITS:
+            raise ValueError(f"tiles_per_launch = {tpl} needs a LOGITS buffer beyond 2^31 - 1 elements")
+        return H, W, ys, xs, tpl
+
+    @torch.no_grad()
+    def _run(self, indices, want: str, metrics=None):
+        pipe = self.pipe
+        if pipe.raw is None:
+            raise RuntimeError("call load() first")
+        H, W, ys, xs, tpl = self._geometry()
+        idx = pipe._stats_index(indices, need_labels=want == "hist")       # ValueError first, then the refusal to run off the GPU
+        dev, K, S, F, NY, NX = pipe.device, self.K, self.S, len(self.flips), len(ys), len(xs)
+        M = idx.numel()
+        blend = torch.empty(M, K, H, W, dtype=torch.float32, device=dev) if want == "blend" else None
+        mask = torch.empty(M, H, W, dtype=torch.int64, device=dev) if want == "mask" else None
+        hist = None
+        if want == "hist":
+            if metrics.hist.device != dev:
+                metrics.hist = metrics.hist.to(dev)
+            hist = metrics.hist
+        w1 = self.profile.to(dev)
+        was_training = isinstance(self.model, torch.nn.Module) and self.model.training
+        if was_training:
+            self.model.eval()
+        try:
+            for g0 in range(0, M, tpl):
+                tiles = idx[g0:g0 + tpl]
+                Mg = tiles.numel()
+                # {tile, y0, x0, flips} of every window in LOGITS order [Mg][F][NY][NX]
+                par = torch.empty(Mg, F, NY, NX, 4, dtype=torch.int32)
+                par[..., 0] = tiles.view(Mg, 1, 1, 1)
+                par[..., 1] = torch.tensor(ys, dtype=torch.int32).view(1, 1, NY, 1)
+                par[..., 2] = torch.tensor(xs, dtype=torch.int32).view(1, 1, 1, NX)
+                par[..., 3] = torch.tensor(self.flips, dtype=torch.int32).view(1, F, 1, 1)
+                par = par.view(-1, 4)
+                n = par.shape[0]
+                logits = torch.empty(n, K, S, S, dtype=torch.float32, device=dev)
+                for b0 in range(0, n, self.wpb):
+                    out = self.model(pipe(params=par[b0:b0 + self.wpb]).x)
+                    b = min(self.wpb, n - b0)
+                    if tuple(out.shape) != (b, K, S, S) or out.dtype != torch.float32:
+                        raise ValueError(f"the model must return float32 [B, {K}, {S}, {S}] logits, got {out.dtype} {tuple(out.shape)}")
+                    logits[b0:b0 + b].copy_(out)
+                self._blend(logits, tiles, ys, xs, w1, H, W,
+                            None if blend is None else blend[g0:g0 + Mg], None if mask is None else mask[g0:g0 + Mg], hist)
+        finally:
+            if was_training:
+                self.model.train()
+        return blend if want == "blend" else mask
+
+    def _blend(self, logits, tiles, ys, xs, w1, H, W, blend, mask, hist) -> None:
+        """one WINDOW_BLEND over a group's LOGITS buffer; YS, XS, FLIPS and INDEX travel in one int32 upload"""
+        pipe, K, S, F, NY, NX, Mg = self.pipe, self.K, self.S, len(self.flips), len(ys), len(xs), tiles.numel()
+        pad = lambda v: v + [0] * (-len(v) % 4)      # noqa: E731
+        ints = pad(list(ys)) + pad(list(xs)) + pad(self.flips)
+        off_xs, off_fl, off_idx = 4 * len(pad(list(ys))), 4 * (len(pad(list(ys))) + len(pad(list(xs)))), 4 * len(ints)
+        aux = torch.cat([torch.tensor(ints, dtype=torch.int32), tiles.to(torch.int32)]).to(pipe.device)
+        i32 = lambda off, n: TRef(D.BASE["AUX"], off, (n,), "i32")      # noqa: E731
+        N = pipe.raw.shape[0]
+        prog = Program()
+        prog.add("WINDOW_BLEND", LOGITS=TRef(D.BASE["X"], 0, (Mg, F, NY, NX, K, S, S)), YS=i32(0, NY), XS=i32(off_xs, NX),
+                 FLIPS=i32(off_fl, F), W1=TRef(D.BASE["CONST"], 0, (S,)),
+                 BLEND=None if blend is None else TRef(D.BASE["OUT"], 0, (Mg, K, H, W)),
+                 MASK=None if mask is None else TRef(D.BASE["DOUT"], 0, (Mg, H, W), "i64"),
+                 LABELS=None if hist is None else TRef(D.BASE["Y"], 0, (N, H, W), "u8"),
+                 INDEX=None if hist is None else i32(off_idx, Mg),
+                 LUT=None if hist is None else TRef(D.BASE["NOISE"], 0, (256,), "i32"),
+                 HIST=None if hist is None else TRef(D.BASE["BUFS"], 0, (K, K), "i64"),
+                 M=Mg, F=F, NY=NY, NX=NX, K=K, H=H, W=W, S=S, NSRC=N, MODE=self.mode)
+        bases = _lib.Bases().set("X", logits).set("AUX", aux).set("CONST", w1)
+        if blend is not None:
+            bases.set("OUT", blend)
+        if mask is not None:
+            bases.set("DOUT", mask)
+        if hist is not None:
+            bases.set("Y", pipe.labels).set("NOISE", pipe.lut).set("BUFS", hist)
+        _lib.run(prog.pack(), bases, torch.cuda.current_stream(pipe.device).cuda_stream)
