@@ -74,6 +74,9 @@ int launch_im2col(const S2kOp&, const Ctx&);
 int launch_tile_label_hist(const S2kOp&, const Ctx&);
 int launch_tile_moments(const S2kOp&, const Ctx&);
 int launch_window_blend(const S2kOp&, const Ctx&);
+int launch_seg_stats(const S2kOp&, const Ctx&);
+int launch_seg_hist(const S2kOp&, const Ctx&);
+int launch_grad_clip(const S2kOp&, const Ctx&);
 int launch_adam(float*, const float*, float*, float*, int64_t, double, double, double, double, double, int, hipStream_t);
 int launch_mfma_selftest(const float*, const float*, float*, hipStream_t);
 
@@ -95,7 +98,8 @@ static const char* const kNames[S2K_N_KINDS + 1] = {
     "BN_RESIDUAL", "CHANNEL_SUM", "LOSS_FWD", "LOSS_BWD", "ARGMAX", "CHAN_LN_FWD", "CHAN_LN_BWD", "ACT_BWD", "ACT_FWD",
     "ATTN_FWD", "ATTN_BWD", "MAE_MASK_INDEX", "IDS_TO_DEC_IDX", "TOKEN_GATHER", "TOKEN_SCATTER", "PATCHIFY", "MAE_LOSS_FWD",
     "MAE_LOSS_BWD", "TRANSPOSE_CL", "CONFUSION", "DROP_GATE", "TILE_PREP", "SE_BN_SUMS", "SE_BN_COMBINE", "SPACE_TO_DEPTH",
-    "UPSAMPLE_ZERO", "SE_FC_WGRAD", "IM2COL", "TILE_LABEL_HIST", "TILE_MOMENTS", "WINDOW_BLEND"};
+    "UPSAMPLE_ZERO", "SE_FC_WGRAD", "IM2COL", "TILE_LABEL_HIST", "TILE_MOMENTS", "WINDOW_BLEND",
+    "SEG_STATS", "SEG_HIST", "GRAD_CLIP"};
 
 static int dispatch(const S2kOp& op, const Ctx& c) {
     switch (op.kind) {
@@ -153,6 +157,9 @@ static int dispatch(const S2kOp& op, const Ctx& c) {
         case S2K_OP_TILE_LABEL_HIST: return launch_tile_label_hist(op, c);
         case S2K_OP_TILE_MOMENTS: return launch_tile_moments(op, c);
         case S2K_OP_WINDOW_BLEND: return launch_window_blend(op, c);
+        case S2K_OP_SEG_STATS: return launch_seg_stats(op, c);
+        case S2K_OP_SEG_HIST: return launch_seg_hist(op, c);
+        case S2K_OP_GRAD_CLIP: return launch_grad_clip(op, c);
         default: set_error("unknown stage kind %d", op.kind); return S2K_ENOSYS;
     }
 }

@@ -273,6 +273,28 @@ OPS: dict[str, tuple[list[str], list[str], list[str], list[str]]] = {
     # 1 <= K <= 32, LOGITS < 2^31 elements.
     "WINDOW_BLEND": (["LOGITS", "YS", "XS", "FLIPS", "W1", "BLEND", "MASK", "LABELS", "INDEX", "LUT", "HIST"], [],
                      ["M", "F", "NY", "NX", "K", "H", "W", "S", "NSRC", "MODE"], []),
+    # per-tensor statistics, histograms and global-norm clipping over a flat f32 buffer X (flat_stats.py; csrc/flat_stats.hip) - what
+    # the reference's `logger.watch(model, log="all")` and `gradient_clip_val` cost a host loop over every tensor (556 gradients for U-Net b5).  All three work on a
+    # segment table SEGS i32 [P][2] = {first float, number of floats >= 1} and a chunk table CHUNKS i32 [NC][2] = {segment, index of the
+    # chunk within it}: segment p is cut into ceil(n / SEG_CHUNK) chunks of SEG_CHUNK = 16384 floats (the last one shorter), the rows
+    # ascend by (segment, index) and one workgroup owns one chunk.  Both tables are built and validated on the host before upload
+    # (flat_stats.build_tables / check_tables), like TILE_PREP's PARAMS; the stages do not range-check them.  No float atomics.
+    #   STATS[p] = {sum, sumsq, min, max}   (f64 [P][4]; sum / min / max over the FINITE elements - none finite: min = +inf, max = -inf -
+    #   sumsq over ALL elements, so a NaN / Inf propagates: torch's norm);   COUNTS[p] = {#NaN, #+-Inf}   (i64 [P][2])
+    # f64 accumulation in a fixed order (per thread in ascending address, a butterfly through the wave, the waves in order, then the
+    # chunk partials PART f64 [NC][6] - scratch - of a segment in ascending order): bit-identical from run to run.
+    "SEG_STATS": (["X", "SEGS", "CHUNKS", "PART", "STATS", "COUNTS"], [], ["P", "NC"], []),
+    # HIST[p][b] += #{finite x in segment p : bin(x) == b}   (i64 [P][NB], 1 <= NB <= 256; accumulates - the caller zeroes it) with
+    # lo = STATS[p][2], hi = STATS[p][3] read from device memory (SEG_STATS ran before; no host in between), all in f64:
+    #   lo == hi: lo -= 1, hi += 1 (torch.histc's rule);   b = floor((x - lo) / (hi - lo) * NB), NB - 1 where that gives NB
+    # Non-finite elements are skipped.  Counted in LDS per workgroup (u32, replicated), flushed with 64-bit integer atomics: exact.
+    "SEG_HIST": (["X", "SEGS", "CHUNKS", "STATS", "HIST"], [], ["P", "NC", "NB"], []),
+    # torch.nn.utils.clip_grad_norm_ (norm_type 2) in place on X, without the host:  total = sum_p STATS[p][1] (ascending p, f64),
+    # norm = sqrt(total), NORM[0] = (float)norm (f32 [1]), coef = MAX_NORM / (norm + 1e-6) in f64, limited to 1 (a NaN stays a NaN),
+    # rounded to f32.  coef >= 1: nothing is written (X stays bit-identical); otherwise X[i] = X[i] * coef over the elements of the
+    # segments only - floats outside every segment are never touched.  APPLY = 0: only NORM is written (X / SEGS / CHUNKS / MAX_NORM
+    # unused); APPLY = 1 needs MAX_NORM positive and finite.
+    "GRAD_CLIP": (["X", "SEGS", "CHUNKS", "STATS", "NORM"], [], ["P", "NC", "APPLY"], ["MAX_NORM"]),
 }
 # Tensor slots a stage WRITES (everything else it only reads).  Used by the planner's side-stream hazard pass (unet_plan.finish_plan:
 # a main-stream stage that writes what an outstanding side-stream stage still reads must wait for the side stream first); a kind
@@ -290,11 +312,12 @@ WRITES: dict[str, tuple[str, ...]] = {
     "MAE_LOSS_FWD": ("LOSS", "ACC"), "MAE_LOSS_BWD": ("DPRED",), "TRANSPOSE_CL": ("Y",), "CONFUSION": ("HIST",), "DROP_GATE": ("GATE",),
     "TILE_PREP": ("X", "Y"), "SE_BN_SUMS": ("DGATE", "PS"), "SE_BN_COMBINE": ("STATS2",), "SPACE_TO_DEPTH": ("Y",), "UPSAMPLE_ZERO": ("Y",),
     "SE_FC_WGRAD": ("DW1", "DB1", "DW2", "DB2"), "IM2COL": ("Y",), "TILE_LABEL_HIST": ("HIST",), "TILE_MOMENTS": ("SUMS", "SDPART"),
-    "WINDOW_BLEND": ("BLEND", "MASK", "HIST"),
+    "WINDOW_BLEND": ("BLEND", "MASK", "HIST"), "SEG_STATS": ("PART", "STATS", "COUNTS"), "SEG_HIST": ("HIST",), "GRAD_CLIP": ("X", "NORM"),
 }
 for _k, _w in WRITES.items():
     assert _k in OPS and all(x in OPS[_k][0] for x in _w), _k
 
+SEG_CHUNK = 16384         # floats per chunk of SEG_STATS / SEG_HIST / GRAD_CLIP (256 threads x 16 quads)
 MOMENTS_BLOCK = 2048      # pixel positions per workgroup of TILE_MOMENTS (256 threads x 8 positions)
 
 
