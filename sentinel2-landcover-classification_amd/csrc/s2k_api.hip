@@ -77,6 +77,10 @@ int launch_window_blend(const S2kOp&, const Ctx&);
 int launch_seg_stats(const S2kOp&, const Ctx&);
 int launch_seg_hist(const S2kOp&, const Ctx&);
 int launch_grad_clip(const S2kOp&, const Ctx&);
+int launch_tile_radix_hist(const S2kOp&, const Ctx&);
+int launch_tile_rank_pick(const S2kOp&, const Ctx&);
+int launch_tile_quicklook(const S2kOp&, const Ctx&);
+int launch_class_overlay(const S2kOp&, const Ctx&);
 int launch_adam(float*, const float*, float*, float*, int64_t, double, double, double, double, double, int, hipStream_t);
 int launch_mfma_selftest(const float*, const float*, float*, hipStream_t);
 
@@ -99,7 +103,7 @@ static const char* const kNames[S2K_N_KINDS + 1] = {
     "ATTN_FWD", "ATTN_BWD", "MAE_MASK_INDEX", "IDS_TO_DEC_IDX", "TOKEN_GATHER", "TOKEN_SCATTER", "PATCHIFY", "MAE_LOSS_FWD",
     "MAE_LOSS_BWD", "TRANSPOSE_CL", "CONFUSION", "DROP_GATE", "TILE_PREP", "SE_BN_SUMS", "SE_BN_COMBINE", "SPACE_TO_DEPTH",
     "UPSAMPLE_ZERO", "SE_FC_WGRAD", "IM2COL", "TILE_LABEL_HIST", "TILE_MOMENTS", "WINDOW_BLEND",
-    "SEG_STATS", "SEG_HIST", "GRAD_CLIP"};
+    "SEG_STATS", "SEG_HIST", "GRAD_CLIP", "TILE_RADIX_HIST", "TILE_RANK_PICK", "TILE_QUICKLOOK", "CLASS_OVERLAY"};
 
 static int dispatch(const S2kOp& op, const Ctx& c) {
     switch (op.kind) {
@@ -160,6 +164,10 @@ static int dispatch(const S2kOp& op, const Ctx& c) {
         case S2K_OP_SEG_STATS: return launch_seg_stats(op, c);
         case S2K_OP_SEG_HIST: return launch_seg_hist(op, c);
         case S2K_OP_GRAD_CLIP: return launch_grad_clip(op, c);
+        case S2K_OP_TILE_RADIX_HIST: return launch_tile_radix_hist(op, c);
+        case S2K_OP_TILE_RANK_PICK: return launch_tile_rank_pick(op, c);
+        case S2K_OP_TILE_QUICKLOOK: return launch_tile_quicklook(op, c);
+        case S2K_OP_CLASS_OVERLAY: return launch_class_overlay(op, c);
         default: set_error("unknown stage kind %d", op.kind); return S2K_ENOSYS;
     }
 }

@@ -19,6 +19,10 @@ resident here, so each is one streaming read on the GPU (stages TILE_MOMENTS / T
 data/dataset_stats.py): `band_mean_std` (calculate_mean_std -> the `mean`, `std` of this class), `class_probabilities`
 (get_class_probabilities -> `EfficientNetConfig.class_distribution`, `losses.get_loss`) and `sample_weights` + `weighted_indices`
 (get_sample_weights + WeightedRandomSampler -> the tile indices given to `draw_params`).
+
+Quicklooks: `quicklook` is the reference's percentile-stretched picture of a crop (src/plotting.py:75-96), `band_percentiles` the
+exact order statistics behind it (per tile, or per band over the dataset) and `zero_fraction` the per-tile nodata share of
+src/experiments/sentinel_EDA.py - a radix select over the resident tiles, no sort and no host copy (data/quicklook.py).
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ import torch
 from .. import _lib
 from ..plan import opdefs as D
 from . import dataset_stats as DS
+from . import quicklook as QL
 from ..plan.program import Program, TRef
 
 # CNES land-cover classes 1..23 grouped as in src/configs/cnes_labell_mappings.py:47-75 (class 0 = outside France)
@@ -244,3 +249,73 @@ class GpuTilePipeline:
         if not self.raw.is_cuda:
             raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
         return DS.weighted_indices(weights, num_samples, generator)
+
+    # ---- exact percentiles and quicklooks of the resident tiles (data/quicklook.py) -------------------------------------------
+    def _loaded_shape(self):
+        if self.raw is None:
+            raise RuntimeError("call load() first")
+        return tuple(int(v) for v in self.raw.shape)
+
+    def band_percentiles(self, q, indices=None, bands=None, pooled: bool = True) -> torch.Tensor:
+        """float64 CPU tensor of exact percentiles `q` (numpy's linear method on the values as float64) of the selected raw tiles:
+        pooled=True [len(bands), len(q)], every band (None = all) over all selected tiles - robust clipping bounds beside
+        `band_mean_std` where clouds and nodata make the moments useless; pooled=False [M, len(q)], per tile over the pixels of
+        `bands` taken jointly (the quicklook's statistic).  A tile listed twice counts twice.  Any number of percentiles: they are
+        selected four at a time (eight ranks per program)."""
+        N, C, H, W = self._loaded_shape()
+        qs = QL.check_q(q)
+        bl = QL.check_bands(range(C) if bands is None else bands, C)
+        idx = self._stats_index(indices, need_labels=False)
+        n = (idx.numel() if pooled else len(bl)) * H * W
+        out = []
+        for i in range(0, len(qs), QL.MAX_RANKS // 2):
+            ranks, frac = QL.rank_plan(qs[i:i + QL.MAX_RANKS // 2], n)
+            out.append(QL.run_selection(self.raw, idx, bl, bool(pooled), ranks, frac)[1].cpu())
+        return torch.cat(out, 1)
+
+    def zero_fraction(self, indices=None, band: int = 0) -> torch.Tensor:
+        """float64 CPU tensor [M]: the share of pixels of `band` that are exactly 0 in every selected tile - the nodata share
+        src/experiments/sentinel_EDA.py:20-27 computes per tile on the CPU, as a fraction."""
+        N, C, H, W = self._loaded_shape()
+        b = QL.check_bands([band], C)[0]
+        idx = self._stats_index(indices, need_labels=False)
+        return QL.run_zero_count(self.raw, idx, b).cpu().double() / float(H * W)
+
+    @torch.no_grad()
+    def quicklook(self, indices=None, params=None, bands=(2, 1, 0), percentile: float = 98.0, whole_tile: bool = False) -> torch.Tensor:
+        """uint8 [B, S, S, 3] (h w rgb) on the device: the reference's percentile-stretched picture of `bands` for every sample -
+        the crop `params` names (the same {tile, y0, x0, flips} array given to `__call__`: the picture is what the model saw), or
+        the centre crop of the tiles `indices` (None = all).  whole_tile=True: [B, H, W, 3], the whole tile (params offsets 0).
+        The bounds are the percentiles (100 - percentile, percentile) over ALL pixels of the three bands of the WHOLE tile jointly,
+        as in src/plotting.py:75-96, then `clip((v - lo) / (hi - lo) * 255, 0, 255)` truncated to uint8, bit for bit numpy's.
+
+        A tile whose two bounds coincide (a constant tile, or one that is mostly nodata) gives a black picture: the reference
+        divides by zero there and stores whatever the cast makes of NaN / inf."""
+        N, C, H, W = self._loaded_shape()
+        bl = QL.check_bands(bands, C, count=3)
+        p = QL.check_percentile(percentile)
+        SH, SW = (H, W) if whole_tile else (self.S, self.S)
+        if params is None:
+            idx = torch.arange(N, dtype=torch.int64) if indices is None else torch.as_tensor(indices, dtype=torch.int64).reshape(-1).cpu()
+            if idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= N:
+                raise ValueError("tile indices out of range (or none given)")
+            params = self.draw_params(idx, training=False)
+            if whole_tile:
+                params[:, 1:3] = 0
+        par = QL.check_params(params, N, H, W, SH, SW)
+        if not self.raw.is_cuda:
+            raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
+        B = par.shape[0]
+        tiles, slot = torch.unique(par[:, 0], return_inverse=True)      # every tile's bounds are selected once
+        ranks, frac = QL.rank_plan([100.0 - p, p], 3 * H * W)
+        out = torch.empty(B, SH, SW, 3, dtype=torch.uint8, device=self.device)
+
+        def stretch(prog, const, ws, pct, bases):
+            prog.add("TILE_QUICKLOOK", RAW=TRef(D.BASE["X"], 0, (N, C, H, W), "i16"), PARAMS=const.put(par, "i32"),
+                     SLOT=const.put(slot.to(torch.int32), "i32"), BANDS=const.put(bl, "i32"), PCT=pct,
+                     OUT=TRef(D.BASE["OUT"], 0, (B, SH, SW, 3), "u8"), B=B, C=C, H=H, W=W, SH=SH, SW=SW, NSRC=N,
+                     NROW=int(tiles.numel()), NQ=2)
+            bases.set("OUT", out)
+
+        QL.run_selection(self.raw, tiles.to(torch.int32), bl, False, ranks, frac, extra=stretch)
+        return out

@@ -295,6 +295,38 @@ OPS: dict[str, tuple[list[str], list[str], list[str], list[str]]] = {
     # segments only - floats outside every segment are never touched.  APPLY = 0: only NORM is written (X / SEGS / CHUNKS / MAX_NORM
     # unused); APPLY = 1 needs MAX_NORM positive and finite.
     "GRAD_CLIP": (["X", "SEGS", "CHUNKS", "STATS", "NORM"], [], ["P", "NC", "APPLY"], ["MAX_NORM"]),
+    # tile quicklooks (data/quicklook.py, render.py; csrc/quicklook.hip): exact order statistics of the resident int16 tiles WITHOUT a
+    # sort - a two-level radix select, 256 bins per level, over key(v) = (uint16)(v + 32768), which keeps the order - as ONE program of
+    # four records (HIST pass 0, PICK step 0, HIST pass 1, PICK step 1; no host in between), the reference's percentile stretch of
+    # src/plotting.py:75-96 and the class overlay of src/train_segmentation.py:166-219.  Integers and f64 in a fixed operation order:
+    # every result is bit-identical to its numpy restatement (tests/quicklook_ref.py) and from run to run.
+    # A GROUP is the multiset a statistic is taken over.  POOLED = 0: G = M groups, group m = all pixels of the bands BANDS[0..NBND) of
+    # tile INDEX[m], jointly (the reference quicklook's meaning).  POOLED = 1: G = NBND groups, group b = band BANDS[b] over all M
+    # selected tiles (a tile listed twice counts twice).  Every group holds N = (POOLED ? M : NBND) * H * W values.
+    #   PASS 0:  HIST[g][key >> 8] += 1                                          (i64 [G][256])
+    #   PASS 1:  HIST[g][r][key & 255] += 1  where key >> 8 == BUCKET[g][r]      (i64 [G][R][256]; BUCKET i32 [G][R], 1 <= R <= 8)
+    # The stage accumulates: the caller zeroes HIST.  RAW i16 [NSRC][C][H][W]; INDEX i32 [M] (any order, duplicates allowed) and BANDS
+    # i32 [NBND] (distinct, in [0, C), 1 <= NBND <= 16) are validated on the host before upload, like TILE_LABEL_HIST's INDEX.
+    "TILE_RADIX_HIST": (["RAW", "INDEX", "BANDS", "BUCKET", "HIST"], [], ["M", "C", "H", "W", "NSRC", "NBND", "POOLED", "PASS", "R"], []),
+    # the selection steps between and after the two counting passes.  RANKS i64 [R], zero-based, 0 <= rank < N (validated on the host).
+    #   STEP 0 (HIST [G][256]):     BUCKET[g][r] = first bin whose inclusive prefix count exceeds RANKS[r];
+    #                               REST[g][r] = RANKS[r] - (count below that bin)                              (i64 [G][R])
+    #   STEP 1 (HIST [G][R][256]):  bin = first bin of HIST[g][r] whose inclusive prefix exceeds REST[g][r];
+    #                               VALUES[g][r] = ((BUCKET[g][r] << 8) | bin) - 32768                          (i32 [G][R]) = sorted(group)[rank]
+    #     PCT[g][q] (f64 [G][R / 2], optional with FRAC f64 [R / 2]) from a = VALUES[g][2q], b = VALUES[g][2q + 1], t = FRAC[q], numpy's
+    #     linear method with separately rounded operations:  d = b - a;  PCT = a + d*t;  t >= 0.5: PCT = b - d*(1 - t)
+    # A HIST that holds fewer than rank + 1 counts (not this program's) selects bin 255.
+    "TILE_RANK_PICK": (["HIST", "RANKS", "BUCKET", "REST", "VALUES", "FRAC", "PCT"], ["N"], ["G", "R", "STEP"], []),
+    # the percentile stretch: for output b, PARAMS[b] = {tile, y0, x0, flips} with TILE_PREP's meaning (validated on the host: the
+    # SH x SW window lies inside the tile), (lo, hi) = PCT[SLOT[b]][0..1] (PCT f64 [NROW][NQ], NQ >= 2; SLOT i32 [B] in [0, NROW)),
+    #   OUT[b][i][j][k] = (uint8) trunc(clip((double(v) - lo) / (hi - lo) * 255.0, 0, 255)),  v = RAW[tile][BANDS[k]][y0 + i'][x0 + j']
+    # (u8 [B][SH][SW][3], h w rgb; i' = vflip ? SH-1-i : i, j' likewise; BANDS i32 [3]) - the operations in exactly this order, in f64.
+    # hi <= lo or a non-finite bound (a constant tile; the reference divides by zero there): OUT = 0.
+    "TILE_QUICKLOOK": (["RAW", "PARAMS", "SLOT", "BANDS", "PCT", "OUT"], [], ["B", "C", "H", "W", "SH", "SW", "NSRC", "NROW", "NQ"], []),
+    # class colours over a picture: CLS i64 [B][SH][SW], PALETTE u8 [K][3] (1 <= K <= 256), BASE u8 [B][SH][SW][3] (absent = black),
+    #   OUT = (BASE*(256 - ALPHA) + PALETTE[CLS]*ALPHA + 128) >> 8   per channel, in integers (u8 [B][SH][SW][3]; 0 <= ALPHA <= 256)
+    # A pixel whose class lies outside [0, K) - and, with SKIP0 = 1, a pixel of class 0 - keeps BASE unchanged.  OUT may be BASE.
+    "CLASS_OVERLAY": (["CLS", "PALETTE", "BASE", "OUT"], [], ["B", "SH", "SW", "K", "ALPHA", "SKIP0"], []),
 }
 # Tensor slots a stage WRITES (everything else it only reads).  Used by the planner's side-stream hazard pass (unet_plan.finish_plan:
 # a main-stream stage that writes what an outstanding side-stream stage still reads must wait for the side stream first); a kind
@@ -313,6 +345,7 @@ WRITES: dict[str, tuple[str, ...]] = {
     "TILE_PREP": ("X", "Y"), "SE_BN_SUMS": ("DGATE", "PS"), "SE_BN_COMBINE": ("STATS2",), "SPACE_TO_DEPTH": ("Y",), "UPSAMPLE_ZERO": ("Y",),
     "SE_FC_WGRAD": ("DW1", "DB1", "DW2", "DB2"), "IM2COL": ("Y",), "TILE_LABEL_HIST": ("HIST",), "TILE_MOMENTS": ("SUMS", "SDPART"),
     "WINDOW_BLEND": ("BLEND", "MASK", "HIST"), "SEG_STATS": ("PART", "STATS", "COUNTS"), "SEG_HIST": ("HIST",), "GRAD_CLIP": ("X", "NORM"),
+    "TILE_RADIX_HIST": ("HIST",), "TILE_RANK_PICK": ("BUCKET", "REST", "VALUES", "PCT"), "TILE_QUICKLOOK": ("OUT",), "CLASS_OVERLAY": ("OUT",),
 }
 for _k, _w in WRITES.items():
     assert _k in OPS and all(x in OPS[_k][0] for x in _w), _k

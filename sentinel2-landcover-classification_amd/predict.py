@@ -19,7 +19,9 @@ import math
 import torch
 
 from . import _lib
+from .data import quicklook as QL
 from .plan import opdefs as D
+from .render import overlay
 from .plan.program import Program, TRef
 
 MAX_CLASSES = 32                 # WINDOW_BLEND keeps a pixel quad's K sums in registers
@@ -103,6 +105,17 @@ class TilePredictor:
         if int(metrics.C) != self.K:
             raise ValueError("metrics.num_classes differs from the predictor's")
         self._run(indices, want="hist", metrics=metrics)
+
+    def render(self, indices, palette, alpha: float = 0.5) -> torch.Tensor:
+        """uint8 [M, H, W, 3] on the device: the whole-tile quicklook of the selected tiles (`GpuTilePipeline.quicklook`, its default
+        bands and percentile) with the predicted class map laid over it in the colours of `palette` (uint8 [>= num_classes, 3]) at
+        opacity `alpha` (`render.overlay`)."""
+        pal = QL.check_palette(palette)
+        QL.alpha_code(alpha)
+        if pal.shape[0] < self.K:
+            raise ValueError("palette needs one colour per class")
+        picture = self.pipe.quicklook(indices, whole_tile=True)          # ValueError first, then the refusal to run off the GPU
+        return overlay(picture, self.predict(indices), pal, alpha)
 
     # ---- implementation ------------------------------------------------------------------------------------------------------
     def _geometry(self):
