@@ -31,11 +31,10 @@ import typing
 import numpy as np
 import torch
 
-from .. import _lib
 from ..plan import opdefs as D
 from . import dataset_stats as DS
 from . import quicklook as QL
-from ..plan.program import Program, TRef
+from ..stage_call import StageCall, cached
 
 # CNES land-cover classes 1..23 grouped as in src/configs/cnes_labell_mappings.py:47-75 (class 0 = outside France)
 _CNES_GROUP = {**{k: "impervious_surface" for k in (1, 2, 3, 4)},
@@ -62,9 +61,21 @@ def label_lut(label_map_name: str) -> torch.Tensor:
     return lut
 
 
+_CALLS = {}      # the packed TILE_PREP calls of this process (stage_call.cached)
+
+
 class S2OSMSample(typing.NamedTuple):
     x: torch.Tensor
     y: torch.Tensor
+
+
+def tile_prep_call(raw, labels, par, norm, lut, x, y) -> StageCall:
+    """TILE_PREP of the crops `par` (int32 [B, 4] on the device) of `raw` into `x` [B, C, S, S]; `y` None: no labels, no LUT"""
+    N, C, H, W = raw.shape
+    call = StageCall()
+    call.add("TILE_PREP", RAW=call.t(raw), LABELS=call.t(labels if y is not None else None), PARAMS=call.t(par), NORM=call.t(norm),
+             LUT=call.t(lut if y is not None else None), X=call.t(x), Y=call.t(y), B=x.shape[0], C=C, H=H, W=W, S=x.shape[2], NSRC=N)
+    return call
 
 
 class GpuTilePipeline:
@@ -131,17 +142,7 @@ class GpuTilePipeline:
         par_d = par.contiguous().to(self.device)
         x = torch.empty(B, C, S, S, dtype=torch.float32, device=self.device)
         y = torch.empty(B, S, S, dtype=torch.int64, device=self.device) if self.labels is not None else None
-        prog = Program()
-        prog.add("TILE_PREP", RAW=TRef(D.BASE["X"], 0, (N, C, H, W), "i16"),
-                 LABELS=TRef(D.BASE["Y"], 0, (N, H, W), "u8") if y is not None else None,
-                 PARAMS=TRef(D.BASE["AUX"], 0, (B, 4), "i32"), NORM=TRef(D.BASE["CONST"], 0, (2, C)),
-                 LUT=TRef(D.BASE["NOISE"], 0, (256,), "i32") if y is not None else None,
-                 X=TRef(D.BASE["OUT"], 0, (B, C, S, S)), Y=TRef(D.BASE["DOUT"], 0, (B, S, S), "i64") if y is not None else None,
-                 B=B, C=C, H=H, W=W, S=S, NSRC=N)
-        bases = _lib.Bases().set("X", self.raw).set("AUX", par_d).set("CONST", self.norm).set("OUT", x)
-        if y is not None:
-            bases.set("Y", self.labels).set("NOISE", self.lut).set("DOUT", y)
-        _lib.run(prog.pack(), bases, torch.cuda.current_stream(self.device).cuda_stream)
+        cached(_CALLS, tile_prep_call, self.raw, self.labels, par_d, self.norm, self.lut, x, y).run()
         if not self.squeeze and self.frames == 1:
             x = x.unsqueeze(2)            # per sample (c, 1, h, w), s2osm_dataset.py:64-66
         return S2OSMSample(x=x, y=y)
@@ -187,12 +188,10 @@ class GpuTilePipeline:
         idx_d = idx.to(self.device)
         sums = torch.zeros(C, 2, dtype=torch.int64, device=self.device)
         sdpart = torch.zeros(C, NB, dtype=torch.float64, device=self.device)
-        prog = Program()
-        prog.add("TILE_MOMENTS", RAW=TRef(D.BASE["X"], 0, (N, C, H, W), "i16"), INDEX=TRef(D.BASE["AUX"], 0, (M,), "i32"),
-                 SUMS=TRef(D.BASE["OUT"], 0, (C, 2), "i64"), SDPART=TRef(D.BASE["DOUT"], 0, (C, NB), "f64"),
+        call = StageCall()
+        call.add("TILE_MOMENTS", RAW=call.t(self.raw), INDEX=call.t(idx_d), SUMS=call.t(sums), SDPART=call.t(sdpart),
                  M=M, C=C, H=H, W=W, NSRC=N, NB=NB)
-        bases = _lib.Bases().set("X", self.raw).set("AUX", idx_d).set("OUT", sums).set("DOUT", sdpart)
-        _lib.run(prog.pack(), bases, torch.cuda.current_stream(self.device).cuda_stream)
+        call.run()
         return sums, sdpart, M, H * W
 
     def band_mean_std(self, indices=None, pooled: bool = False):
@@ -217,12 +216,10 @@ class GpuTilePipeline:
         N, H, W = self.labels.shape
         idx_d = idx.to(self.device)
         hist = torch.zeros(M, K, dtype=torch.int64, device=self.device)
-        prog = Program()
-        prog.add("TILE_LABEL_HIST", LABELS=TRef(D.BASE["Y"], 0, (N, H, W), "u8"), INDEX=TRef(D.BASE["AUX"], 0, (M,), "i32"),
-                 LUT=TRef(D.BASE["NOISE"], 0, (256,), "i32"), HIST=TRef(D.BASE["OUT"], 0, (M, K), "i64"),
+        call = StageCall()
+        call.add("TILE_LABEL_HIST", LABELS=call.t(self.labels), INDEX=call.t(idx_d), LUT=call.t(self.lut), HIST=call.t(hist),
                  M=M, H=H, W=W, K=K, Y0=y0, X0=x0, WH=wh, WW=ww, NSRC=N)
-        bases = _lib.Bases().set("Y", self.labels).set("AUX", idx_d).set("NOISE", self.lut).set("OUT", hist)
-        _lib.run(prog.pack(), bases, torch.cuda.current_stream(self.device).cuda_stream)
+        call.run()
         return hist
 
     def class_probabilities(self, num_classes: int, ignore_zero_label: bool, indices=None, max_tiles: int = 2500,
@@ -310,12 +307,6 @@ class GpuTilePipeline:
         ranks, frac = QL.rank_plan([100.0 - p, p], 3 * H * W)
         out = torch.empty(B, SH, SW, 3, dtype=torch.uint8, device=self.device)
 
-        def stretch(prog, const, ws, pct, bases):
-            prog.add("TILE_QUICKLOOK", RAW=TRef(D.BASE["X"], 0, (N, C, H, W), "i16"), PARAMS=const.put(par, "i32"),
-                     SLOT=const.put(slot.to(torch.int32), "i32"), BANDS=const.put(bl, "i32"), PCT=pct,
-                     OUT=TRef(D.BASE["OUT"], 0, (B, SH, SW, 3), "u8"), B=B, C=C, H=H, W=W, SH=SH, SW=SW, NSRC=N,
-                     NROW=int(tiles.numel()), NQ=2)
-            bases.set("OUT", out)
-
-        QL.run_selection(self.raw, tiles.to(torch.int32), bl, False, ranks, frac, extra=stretch)
+        QL.run_selection(self.raw, tiles.to(torch.int32), bl, False, ranks, frac,
+                         extra=lambda call, pct: QL.add_quicklook(call, self.raw, par, slot, bl, pct, out, int(tiles.numel())))
         return out

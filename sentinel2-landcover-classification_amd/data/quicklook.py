@@ -1,6 +1,6 @@
 """Host side of the tile quicklooks: the rank / fraction derivation of numpy's linear percentile, the argument validators of
-`GpuTilePipeline.band_percentiles` / `.zero_fraction` / `.quicklook`, `render.overlay` and `TilePredictor.render`, and the one program
-builder behind them (`run_selection`).  Pure host code except `run_selection`, which launches.
+`GpuTilePipeline.band_percentiles` / `.zero_fraction` / `.quicklook`, `render.overlay` and `TilePredictor.render`, and the stage calls
+behind them (`run_selection`, `run_zero_count`, `add_quicklook`; stage_call.py).  Pure host code except the two `run_*`, which launch.
 
 What it replaces in the reference: the picture side of `log_image_metrics` / `_log_segmentation_pred`
 (src/train_segmentation.py:166-219) and src/plotting.py:75-96,
@@ -25,9 +25,8 @@ import math
 import numpy as np
 import torch
 
-from .. import _lib
-from ..plan import opdefs as D
-from ..plan.program import ALIGN, ITEMSIZE, Program, TRef
+from ..plan.program import TRef
+from ..stage_call import StageCall
 
 MAX_RANKS = 8          # ranks per selection program (TILE_RANK_PICK's R): four percentiles
 MAX_BANDS = 16         # TILE_RADIX_HIST's NBND
@@ -123,42 +122,12 @@ def check_params(params, N: int, H: int, W: int, SH: int, SW: int) -> torch.Tens
     return par.to(torch.int32).contiguous()
 
 
-class _Buf:
-    """A byte image laid out like an arena: constants are `put`, results are `alloc`ated."""
-
-    def __init__(self, base: str):
-        self.base, self.top, self.parts = D.BASE[base], 0, []
-
-    def alloc(self, shape, dtype: str) -> TRef:
-        t = TRef(self.base, self.top, tuple(int(s) for s in shape), dtype)
-        self.top += (t.nbytes + ALIGN - 1) // ALIGN * ALIGN
-        return t
-
-    def put(self, values, dtype: str, shape=None) -> TRef:
-        tdt = {"i32": torch.int32, "i64": torch.int64, "f64": torch.float64}[dtype]
-        data = torch.as_tensor(values, dtype=tdt).contiguous()
-        ref = self.alloc(data.shape if shape is None else shape, dtype)
-        assert ref.nbytes == data.numel() * ITEMSIZE[dtype]
-        self.parts.append((ref.off, data.reshape(-1).view(torch.uint8)))
-        return ref
-
-    def image(self) -> torch.Tensor:
-        img = torch.zeros(max(self.top, ALIGN), dtype=torch.uint8)
-        for off, b in self.parts:
-            img[off:off + b.numel()] = b
-        return img
-
-
-def view(ws: torch.Tensor, ref: TRef, dtype: torch.dtype) -> torch.Tensor:
-    return ws[ref.off:ref.off + ref.nbytes].view(dtype).view(ref.shape)
-
-
 @torch.no_grad()
 def run_selection(raw: torch.Tensor, index: torch.Tensor, bands: list[int], pooled: bool, ranks: list[int], frac: list[float] | None,
                   extra=None):
-    """The four-record selection program over the resident tiles `raw` (on the GPU): (VALUES int32 [G, R], PCT float64 [G, R // 2] or
-    None) as views of one device workspace.  `index` int32 CPU [M] and `bands` are validated by the caller.  `extra(prog, const, ws,
-    pct_ref, bases)` may append records that read PCT in the same program (the quicklook stretch) before anything is launched."""
+    """The four-record selection call over the resident tiles `raw` (on the GPU): (VALUES int32 [G, R], PCT float64 [G, R // 2] or
+    None) as views of the call's zeroed scratch.  `index` int32 CPU [M] and `bands` are validated by the caller.  `extra(call, pct_ref)`
+    may append records that read PCT in the same call (the quicklook stretch) before anything is uploaded or launched."""
     nsrc, C, H, W = raw.shape
     M, nb, R = int(index.numel()), len(bands), len(ranks)
     if not 1 <= R <= MAX_RANKS:
@@ -166,26 +135,31 @@ def run_selection(raw: torch.Tensor, index: torch.Tensor, bands: list[int], pool
     G, N = (nb, M * H * W) if pooled else (M, nb * H * W)
     if any(not 0 <= r < N for r in ranks):
         raise ValueError("rank outside the group")
-    const, ws = _Buf("AUX"), _Buf("WS")
-    t_index, t_bands, t_ranks = const.put(index, "i32"), const.put(bands, "i32"), const.put(ranks, "i64")
-    t_frac = const.put(frac, "f64") if frac is not None else None
-    t_raw = TRef(D.BASE["X"], 0, (nsrc, C, H, W), "i16")
-    h0, h1 = ws.alloc((G, 256), "i64"), ws.alloc((G, R, 256), "i64")
-    bucket, rest, values = ws.alloc((G, R), "i32"), ws.alloc((G, R), "i64"), ws.alloc((G, R), "i32")
-    pct = ws.alloc((G, R // 2), "f64") if frac is not None else None
-    prog = Program()
+    call = StageCall()
+    t_raw = call.t(raw)
+    t_index, t_bands, t_ranks = call.const(index, "i32"), call.const(bands, "i32"), call.const(ranks, "i64")
+    t_frac = call.const(frac, "f64") if frac is not None else None
+    h0, h1 = call.scratch((G, 256), "i64"), call.scratch((G, R, 256), "i64")          # HIST accumulates: the scratch is zeroed
+    bucket, rest, values = call.scratch((G, R), "i32"), call.scratch((G, R), "i64"), call.scratch((G, R), "i32")
+    pct = call.scratch((G, R // 2), "f64") if frac is not None else None
     dims = dict(M=M, C=C, H=H, W=W, NSRC=nsrc, NBND=nb, POOLED=int(pooled), R=R)
-    prog.add("TILE_RADIX_HIST", RAW=t_raw, INDEX=t_index, BANDS=t_bands, BUCKET=None, HIST=h0, PASS=0, **dims)
-    prog.add("TILE_RANK_PICK", HIST=h0, RANKS=t_ranks, BUCKET=bucket, REST=rest, N=N, G=G, R=R, STEP=0)
-    prog.add("TILE_RADIX_HIST", RAW=t_raw, INDEX=t_index, BANDS=t_bands, BUCKET=bucket, HIST=h1, PASS=1, **dims)
-    prog.add("TILE_RANK_PICK", HIST=h1, RANKS=t_ranks, BUCKET=bucket, REST=rest, VALUES=values, FRAC=t_frac, PCT=pct, N=N, G=G, R=R, STEP=1)
-    bases = _lib.Bases().set("X", raw)
+    call.add("TILE_RADIX_HIST", RAW=t_raw, INDEX=t_index, BANDS=t_bands, BUCKET=None, HIST=h0, PASS=0, **dims)
+    call.add("TILE_RANK_PICK", HIST=h0, RANKS=t_ranks, BUCKET=bucket, REST=rest, N=N, G=G, R=R, STEP=0)
+    call.add("TILE_RADIX_HIST", RAW=t_raw, INDEX=t_index, BANDS=t_bands, BUCKET=bucket, HIST=h1, PASS=1, **dims)
+    call.add("TILE_RANK_PICK", HIST=h1, RANKS=t_ranks, BUCKET=bucket, REST=rest, VALUES=values, FRAC=t_frac, PCT=pct, N=N, G=G, R=R, STEP=1)
     if extra is not None:
-        extra(prog, const, ws, pct, bases)
-    ws_d = torch.zeros(max(ws.top, ALIGN), dtype=torch.uint8, device=raw.device)      # HIST accumulates: zeroed here
-    bases.set("AUX", const.image().to(raw.device)).set("WS", ws_d)
-    _lib.run(prog.pack(), bases, torch.cuda.current_stream(raw.device).cuda_stream)
-    return view(ws_d, values, torch.int32), (None if pct is None else view(ws_d, pct, torch.float64))
+        extra(call, pct)
+    call.run()
+    return call.view(values), (None if pct is None else call.view(pct))
+
+
+def add_quicklook(call: StageCall, raw, par, slot, bands, pct: TRef, out, nrow: int) -> None:
+    """Append the TILE_QUICKLOOK record that stretches the crops `par` (int32 CPU [B, 4]) of `raw` into `out` (uint8 [B, SH, SW, 3])
+    between the bounds PCT[slot[b]] (`pct`: a ref of `call`, float64 [nrow, 2])."""
+    N, C, H, W = raw.shape
+    B, SH, SW = out.shape[:3]
+    call.add("TILE_QUICKLOOK", RAW=call.t(raw), PARAMS=call.const(par, "i32"), SLOT=call.const(slot, "i32"), BANDS=call.const(bands, "i32"),
+             PCT=pct, OUT=call.t(out), B=B, C=C, H=H, W=W, SH=SH, SW=SW, NSRC=N, NROW=nrow, NQ=2)
 
 
 @torch.no_grad()
@@ -194,14 +168,9 @@ def run_zero_count(raw: torch.Tensor, index: torch.Tensor, band: int) -> torch.T
     preset to that of the value 0, whose fine bin 0 then is the count."""
     nsrc, C, H, W = raw.shape
     M = int(index.numel())
-    const, ws = _Buf("AUX"), _Buf("WS")
-    t_index, t_bands = const.put(index, "i32"), const.put([band], "i32")
-    t_bucket = const.put([ZERO_BUCKET] * M, "i32", (M, 1))
-    hist = ws.alloc((M, 1, 256), "i64")
-    prog = Program()
-    prog.add("TILE_RADIX_HIST", RAW=TRef(D.BASE["X"], 0, (nsrc, C, H, W), "i16"), INDEX=t_index, BANDS=t_bands, BUCKET=t_bucket, HIST=hist,
-             M=M, C=C, H=H, W=W, NSRC=nsrc, NBND=1, POOLED=0, PASS=1, R=1)
-    ws_d = torch.zeros(ws.top, dtype=torch.uint8, device=raw.device)
-    bases = _lib.Bases().set("X", raw).set("AUX", const.image().to(raw.device)).set("WS", ws_d)
-    _lib.run(prog.pack(), bases, torch.cuda.current_stream(raw.device).cuda_stream)
-    return view(ws_d, hist, torch.int64)[:, 0, 0]
+    call = StageCall()
+    hist = call.scratch((M, 1, 256), "i64")
+    call.add("TILE_RADIX_HIST", RAW=call.t(raw), INDEX=call.const(index, "i32"), BANDS=call.const([band], "i32"),
+             BUCKET=call.const([ZERO_BUCKET] * M, "i32", (M, 1)), HIST=hist, M=M, C=C, H=H, W=W, NSRC=nsrc, NBND=1, POOLED=0, PASS=1, R=1)
+    call.run()
+    return call.view(hist)[:, 0, 0]

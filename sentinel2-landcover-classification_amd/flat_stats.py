@@ -23,9 +23,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
 from .plan import opdefs as D
-from .plan.program import Program, TRef
+from .stage_call import StageCall
 
 CHUNK = D.SEG_CHUNK          # floats per workgroup of the three stages
 MAX_BINS = 256
@@ -84,7 +83,7 @@ def select(module, gradients: bool, plist=None):
 
 
 class _Tables:
-    """the device side of one selection: SEGS and CHUNKS in one int32 upload, SEG_STATS's scratch"""
+    """the device side of one selection: SEGS and CHUNKS in one upload, SEG_STATS's scratch, the packed calls"""
 
     def __init__(self, names, segments, total: int, device):
         self.names, self.numel = list(names), [n for _, n in segments]
@@ -92,13 +91,11 @@ class _Tables:
         check_tables(segs, chunks, total)
         self.segs, self.chunks = segs, chunks
         self.P, self.NC = len(segs), len(chunks)
-        self.off_chunks = (self.P * 2 + 3) // 4 * 16          # bytes: CHUNKS starts on a 16-byte boundary behind SEGS
-        host = np.zeros(self.off_chunks // 4 + self.NC * 2, dtype=np.int32)
-        host[:self.P * 2] = segs.reshape(-1)
-        host[self.off_chunks // 4:] = chunks.reshape(-1)
-        self.aux = torch.from_numpy(host).to(device)
-        self.part = torch.empty(self.NC * 6, dtype=torch.float64, device=device)
-        self.programs = {}          # packed records per call kind (FlatStats._program)
+        tab = StageCall()           # only its byte image is used: uploaded here, once, and bound as raw bytes by every call
+        self.segs_off, self.chunks_off = tab.const(segs, "i32").off, tab.const(chunks, "i32").off
+        self.aux = tab.image().to(device)
+        self.part = torch.empty(self.NC, 6, dtype=torch.float64, device=device)
+        self.calls = {}             # the packed calls over these tables (FlatStats._call)
 
 
 class SegmentStats:
@@ -188,25 +185,30 @@ class FlatStats:
             self._tables[gradients] = hit
         return buf, hit[1]
 
-    def _program(self, t: _Tables, total: int, hist: bool = False, clip: str | None = None):
-        """the packed records of one call, cached with the tables: SEG_STATS, then SEG_HIST (hist) or GRAD_CLIP (clip = "norm": the
-        norm only; "apply": MAX_NORM is written into the record per call)"""
-        key = (hist, clip)
-        packed = t.programs.get(key)
-        if packed is None:
-            refs = dict(SEGS=TRef(D.BASE["AUX"], 0, (t.P, 2), "i32"), CHUNKS=TRef(D.BASE["AUX"], t.off_chunks, (t.NC, 2), "i32"),
-                        STATS=TRef(D.BASE["OUT"], 0, (t.P, 4), "f64"), P=t.P, NC=t.NC)
-            x = TRef(D.BASE["X"], 0, (total,))
-            prog = Program()
-            prog.add("SEG_STATS", X=x, PART=TRef(D.BASE["WS"], 0, (t.NC, 6), "f64"), COUNTS=TRef(D.BASE["DOUT"], 0, (t.P, 2), "i64"), **refs)
-            if hist:
-                prog.add("SEG_HIST", X=x, HIST=TRef(D.BASE["BUFS"], 0, (t.P, self.bins), "i64"), NB=self.bins, **refs)
-            if clip == "norm":
-                prog.add("GRAD_CLIP", STATS=refs["STATS"], NORM=TRef(D.BASE["CONST"], 0, (1,)), P=t.P, NC=t.NC, APPLY=0)
-            elif clip == "apply":
-                prog.add("GRAD_CLIP", X=x, NORM=TRef(D.BASE["CONST"], 0, (1,)), APPLY=1, MAX_NORM=1.0, **refs)
-            packed = t.programs[key] = prog.pack()
-        return packed
+    def _call(self, t: _Tables, hist: bool, clip: str | None, buf, stats, counts, last) -> StageCall:
+        """SEG_STATS, then SEG_HIST (hist; last = HIST) or GRAD_CLIP (clip = "norm": the norm only, "apply": MAX_NORM is written into
+        the record per call; last = NORM).  The tables fix every shape, so the call is packed once per kind and kept with them; a
+        later use only puts its own tensors behind the slots."""
+        hit = t.calls.get((hist, clip))
+        if hit is not None:
+            for ref, tensor in zip(hit[1], (buf, stats, counts, last)):
+                if ref is not None:
+                    hit[0].rebind(ref, tensor)
+            return hit[0]
+        call = StageCall()
+        x, st, cn, ls = call.t(buf), call.t(stats), call.t(counts), call.t(last)
+        refs = dict(SEGS=call.t(t.aux, (t.P, 2), "i32", t.segs_off), CHUNKS=call.t(t.aux, (t.NC, 2), "i32", t.chunks_off), STATS=st,
+                    P=t.P, NC=t.NC)
+        call.add("SEG_STATS", X=x, PART=call.t(t.part), COUNTS=cn, **refs)
+        if hist:
+            call.add("SEG_HIST", X=x, HIST=ls, NB=self.bins, **refs)
+        if clip == "norm":
+            call.add("GRAD_CLIP", STATS=st, NORM=ls, P=t.P, NC=t.NC, APPLY=0)
+        elif clip == "apply":
+            call.add("GRAD_CLIP", X=x, NORM=ls, APPLY=1, MAX_NORM=1.0, **refs)
+        call.pack()
+        t.calls[(hist, clip)] = call, (x, st, cn, ls)
+        return call
 
     def _run(self, gradients: bool, hist: bool) -> SegmentStats:
         buf, t = self._select(gradients)
@@ -214,10 +216,7 @@ class FlatStats:
         stats = torch.empty(t.P, 4, dtype=torch.float64, device=dev)
         counts = torch.empty(t.P, 2, dtype=torch.int64, device=dev)
         hst = torch.zeros(t.P, self.bins, dtype=torch.int64, device=dev) if hist else None
-        bases = _lib.Bases().set("X", buf).set("AUX", t.aux).set("WS", t.part).set("OUT", stats).set("DOUT", counts)
-        if hist:
-            bases.set("BUFS", hst)
-        _lib.run(self._program(t, buf.numel(), hist=hist), bases, torch.cuda.current_stream(dev).cuda_stream)
+        self._call(t, hist, None, buf, stats, counts, hst).run()
         return SegmentStats(t.names, t.numel, stats, counts, hst)
 
     def _norm(self, max_norm: float | None) -> torch.Tensor:
@@ -227,11 +226,10 @@ class FlatStats:
         stats = torch.empty(t.P, 4, dtype=torch.float64, device=dev)
         counts = torch.empty(t.P, 2, dtype=torch.int64, device=dev)
         norm = torch.empty(1, dtype=torch.float32, device=dev)
-        packed = self._program(t, buf.numel(), clip="norm" if max_norm is None else "apply")
+        call = self._call(t, False, "norm" if max_norm is None else "apply", buf, stats, counts, norm)
         if max_norm is not None:
-            packed[1]["f"][D.slot("GRAD_CLIP", "MAX_NORM")[1]] = max_norm
-        bases = _lib.Bases().set("X", buf).set("AUX", t.aux).set("WS", t.part).set("OUT", stats).set("DOUT", counts).set("CONST", norm)
-        _lib.run(packed, bases, torch.cuda.current_stream(dev).cuda_stream)
+            call.packed[1]["f"][D.slot("GRAD_CLIP", "MAX_NORM")[1]] = max_norm
+        call.run()
         return norm.view(())
 
 

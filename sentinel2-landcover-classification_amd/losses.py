@@ -14,13 +14,11 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
-from .engine import _stream
-from .plan import opdefs as D
-from .plan.program import Program, TRef
+from .stage_call import StageCall, cached
 
 Loss = typing.Callable[[torch.Tensor, torch.Tensor], torch.Tensor]
 ReduceType = typing.Literal["mean", "sum"]
+_CALLS = {}      # the packed LOSS_FWD / LOSS_BWD / ARGMAX calls of this process (stage_call.cached)
 
 
 class LossType(str, enum.Enum):
@@ -41,17 +39,17 @@ def _check(logits: torch.Tensor, y: torch.Tensor):
     return B, C, H * W
 
 
-def _records(B, C, HW, mode, ignore, reduce_sum, gamma, smooth, has_alpha):
-    f32 = lambda base, shape, dt="f32": TRef(D.BASE[base], 0, shape, dt)  # noqa: E731
-    common = dict(B=B, C=C, HW=HW, MODE=mode, IGNORE=ignore, REDUCE_SUM=int(reduce_sum), GAMMA=gamma, SMOOTH=smooth)
-    alpha = f32("CONST", (C,)) if has_alpha else None
-    acc = TRef(D.BASE["WS"], 0, (2,), "f64")
-    loss = TRef(D.BASE["WS"], 16, (1,), "f32")
-    fwd, bwd = Program("loss_fwd"), Program("loss_bwd")
-    fwd.add("LOSS_FWD", LOGITS=f32("X", (B, C, HW)), LABELS=f32("Y", (B, HW), "i64"), ALPHA=alpha, LOSS=loss, ACC=acc, **common)
-    bwd.add("LOSS_BWD", LOGITS=f32("X", (B, C, HW)), LABELS=f32("Y", (B, HW), "i64"), ALPHA=alpha, ACC=acc,
-            GOUT=f32("DOUT", (1,)), DLOGITS=f32("OUT", (B, C, HW)), **common)
-    return fwd.pack(), bwd.pack()
+def loss_call(logits, y, alpha, scratch, gout=None, dlogits=None, **common) -> StageCall:
+    """LOSS_FWD, or with `dlogits` LOSS_BWD, over `scratch`: 32 raw bytes = {f64 num, f64 den, f32 loss}; `common`: the dims and
+    floats both records share"""
+    B, C, HW = common["B"], common["C"], common["HW"]
+    call = StageCall()
+    refs = dict(LOGITS=call.t(logits, (B, C, HW)), LABELS=call.t(y, (B, HW)), ALPHA=call.t(alpha), ACC=call.t(scratch, (2,), "f64"))
+    if dlogits is None:
+        call.add("LOSS_FWD", LOSS=call.t(scratch, (1,), "f32", 16), **refs, **common)
+    else:
+        call.add("LOSS_BWD", GOUT=call.t(gout), DLOGITS=call.t(dlogits, (B, C, HW)), **refs, **common)
+    return call
 
 
 class _PixelLoss(torch.autograd.Function):
@@ -59,14 +57,12 @@ class _PixelLoss(torch.autograd.Function):
     def forward(ctx, logits, y, alpha, mode, ignore, reduce_sum, gamma, smooth):
         B, C, HW = _check(logits, y)
         logits, y = logits.contiguous(), y.contiguous()
-        fwd, bwd = _records(B, C, HW, mode, ignore, reduce_sum, gamma, smooth, alpha is not None)
-        scratch = torch.empty(32, dtype=torch.uint8, device=logits.device)  # {f64 num, f64 den, f32 loss}
-        bases = _lib.Bases().set("X", logits).set("Y", y).set("WS", scratch)
+        common = dict(B=B, C=C, HW=HW, MODE=mode, IGNORE=ignore, REDUCE_SUM=int(reduce_sum), GAMMA=gamma, SMOOTH=smooth)
+        scratch = torch.empty(32, dtype=torch.uint8, device=logits.device)
         if alpha is not None:
             alpha = alpha.to(device=logits.device, dtype=torch.float32).contiguous()
-            bases.set("CONST", alpha)
-        _lib.run(fwd, bases, _stream(logits.device))
-        ctx.bwd, ctx.alpha, ctx.scratch = bwd, alpha, scratch
+        cached(_CALLS, loss_call, logits, y, alpha, scratch, **common).run()
+        ctx.common, ctx.alpha, ctx.scratch = common, alpha, scratch
         ctx.save_for_backward(logits, y)
         return scratch[16:20].view(torch.float32).clone().reshape(())
 
@@ -75,10 +71,7 @@ class _PixelLoss(torch.autograd.Function):
         logits, y = ctx.saved_tensors
         dlogits = torch.empty_like(logits)
         gout = gout.to(torch.float32).contiguous().reshape(1)
-        bases = _lib.Bases().set("X", logits).set("Y", y).set("WS", ctx.scratch).set("DOUT", gout).set("OUT", dlogits)
-        if ctx.alpha is not None:
-            bases.set("CONST", ctx.alpha)
-        _lib.run(ctx.bwd, bases, _stream(logits.device))
+        cached(_CALLS, loss_call, logits, y, ctx.alpha, ctx.scratch, gout, dlogits, **ctx.common).run()
         return dlogits, None, None, None, None, None, None, None
 
 
@@ -134,10 +127,15 @@ def class_mask(logits: torch.Tensor) -> torch.Tensor:
     B, C, H, W = logits.shape
     logits = logits.contiguous()
     mask = torch.empty((B, H, W), dtype=torch.int64, device=logits.device)
-    p = Program("argmax")
-    p.add("ARGMAX", LOGITS=TRef(D.BASE["X"], 0, (B, C, H * W)), MASK=TRef(D.BASE["OUT"], 0, (B, H * W), "i64"), B=B, C=C, HW=H * W)
-    _lib.run(p.pack(), _lib.Bases().set("X", logits).set("OUT", mask), _stream(logits.device))
+    cached(_CALLS, argmax_call, logits, mask).run()
     return mask
+
+
+def argmax_call(logits, mask) -> StageCall:
+    B, C, H, W = logits.shape
+    call = StageCall()
+    call.add("ARGMAX", LOGITS=call.t(logits, (B, C, H * W)), MASK=call.t(mask, (B, H * W)), B=B, C=C, HW=H * W)
+    return call
 
 
 def loss_class_weights(config) -> torch.Tensor | None:

@@ -12,9 +12,9 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
-from .plan import opdefs as D
-from .plan.program import Program, TRef
+from .stage_call import StageCall, cached
+
+_CALLS = {}      # the packed CONFUSION calls of this process (stage_call.cached)
 
 
 class SegMetrics:
@@ -35,16 +35,18 @@ class SegMetrics:
         if self.hist.device != predictions.device:
             self.hist = self.hist.to(predictions.device)
         predictions, labels = predictions.contiguous(), labels.contiguous()
-        n = predictions.numel()
-        prog = Program()
-        prog.add("CONFUSION", PRED=TRef(D.BASE["X"], 0, (n,), "i64"), LABELS=TRef(D.BASE["Y"], 0, (n,), "i64"),
-                 HIST=TRef(D.BASE["OUT"], 0, (self.C * self.C,), "i64"), COUNT=n, C=self.C)
-        bases = _lib.Bases().set("X", predictions).set("Y", labels).set("OUT", self.hist)
-        _lib.run(prog.pack(), bases, torch.cuda.current_stream(predictions.device).cuda_stream)
+        cached(_CALLS, confusion_call, predictions, labels, self.hist, C=self.C).run()
 
     def compute(self) -> dict:
         """{"confusion_matrix" [C,C] rows normalised over the true class, "iou", "accuracy", "f1"} as CPU tensors."""
         return metrics_from_hist(self.hist.view(self.C, self.C).cpu(), self.ignore_index)
+
+
+def confusion_call(predictions, labels, hist, C: int) -> StageCall:
+    n = predictions.numel()
+    call = StageCall()
+    call.add("CONFUSION", PRED=call.t(predictions, (n,)), LABELS=call.t(labels, (n,)), HIST=call.t(hist), COUNT=n, C=C)
+    return call
 
 
 def metrics_from_hist(h: torch.Tensor, ignore_index: int | None) -> dict:

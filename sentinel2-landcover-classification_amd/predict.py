@@ -18,11 +18,9 @@ import math
 
 import torch
 
-from . import _lib
 from .data import quicklook as QL
-from .plan import opdefs as D
 from .render import overlay
-from .plan.program import Program, TRef
+from .stage_call import StageCall
 
 MAX_CLASSES = 32                 # WINDOW_BLEND keeps a pixel quad's K sums in registers
 MAX_LOGITS = (1 << 31) - 1       # elements of one LOGITS buffer (the stage's bound)
@@ -61,6 +59,19 @@ def window_profile(S: int, kind: str = "hann") -> torch.Tensor:
         raise ValueError("window must be 'hann' or 'uniform'")
     half = [math.sin(math.pi * (i + 0.5) / S) ** 2 for i in range((S + 1) // 2)]
     return torch.tensor(half + half[:S // 2][::-1], dtype=torch.float64).to(torch.float32)      # mirrored: symmetric bit for bit
+
+
+def add_window_blend(call: StageCall, logits, ys, xs, flips, w1, mode: int, H: int, W: int, nsrc: int, blend=None, mask=None,
+                     labels=None, index=None, lut=None, hist=None) -> None:
+    """Append the WINDOW_BLEND record over `logits` [M, F, NY, NX, K, S, S] into BLEND [M, K, H, W] and / or MASK [M, H, W]; with `hist`
+    ([K, K] int64) the confusion counts against `lut[labels[index]]`.  YS, XS, FLIPS and INDEX are host values: they travel in the call's
+    one upload."""
+    M, F, NY, NX, K, S = logits.shape[:6]
+    call.add("WINDOW_BLEND", LOGITS=call.t(logits), YS=call.const(ys, "i32"), XS=call.const(xs, "i32"), FLIPS=call.const(flips, "i32"),
+             W1=call.t(w1), BLEND=call.t(blend, (M, K, H, W)), MASK=call.t(mask, (M, H, W)),
+             LABELS=call.t(labels if hist is not None else None), INDEX=call.const(index, "i32") if hist is not None else None,
+             LUT=call.t(lut if hist is not None else None), HIST=call.t(hist, (K, K)),
+             M=M, F=F, NY=NY, NX=NX, K=K, H=H, W=W, S=S, NSRC=nsrc, MODE=mode)
 
 
 class TilePredictor:
@@ -178,29 +189,8 @@ class TilePredictor:
         return blend if want == "blend" else mask
 
     def _blend(self, logits, tiles, ys, xs, w1, H, W, blend, mask, hist) -> None:
-        """one WINDOW_BLEND over a group's LOGITS buffer; YS, XS, FLIPS and INDEX travel in one int32 upload"""
-        pipe, K, S, F, NY, NX, Mg = self.pipe, self.K, self.S, len(self.flips), len(ys), len(xs), tiles.numel()
-        pad = lambda v: v + [0] * (-len(v) % 4)      # noqa: E731
-        ints = pad(list(ys)) + pad(list(xs)) + pad(self.flips)
-        off_xs, off_fl, off_idx = 4 * len(pad(list(ys))), 4 * (len(pad(list(ys))) + len(pad(list(xs)))), 4 * len(ints)
-        aux = torch.cat([torch.tensor(ints, dtype=torch.int32), tiles.to(torch.int32)]).to(pipe.device)
-        i32 = lambda off, n: TRef(D.BASE["AUX"], off, (n,), "i32")      # noqa: E731
-        N = pipe.raw.shape[0]
-        prog = Program()
-        prog.add("WINDOW_BLEND", LOGITS=TRef(D.BASE["X"], 0, (Mg, F, NY, NX, K, S, S)), YS=i32(0, NY), XS=i32(off_xs, NX),
-                 FLIPS=i32(off_fl, F), W1=TRef(D.BASE["CONST"], 0, (S,)),
-                 BLEND=None if blend is None else TRef(D.BASE["OUT"], 0, (Mg, K, H, W)),
-                 MASK=None if mask is None else TRef(D.BASE["DOUT"], 0, (Mg, H, W), "i64"),
-                 LABELS=None if hist is None else TRef(D.BASE["Y"], 0, (N, H, W), "u8"),
-                 INDEX=None if hist is None else i32(off_idx, Mg),
-                 LUT=None if hist is None else TRef(D.BASE["NOISE"], 0, (256,), "i32"),
-                 HIST=None if hist is None else TRef(D.BASE["BUFS"], 0, (K, K), "i64"),
-                 M=Mg, F=F, NY=NY, NX=NX, K=K, H=H, W=W, S=S, NSRC=N, MODE=self.mode)
-        bases = _lib.Bases().set("X", logits).set("AUX", aux).set("CONST", w1)
-        if blend is not None:
-            bases.set("OUT", blend)
-        if mask is not None:
-            bases.set("DOUT", mask)
-        if hist is not None:
-            bases.set("Y", pipe.labels).set("NOISE", pipe.lut).set("BUFS", hist)
-        _lib.run(prog.pack(), bases, torch.cuda.current_stream(pipe.device).cuda_stream)
+        """one WINDOW_BLEND over a group's LOGITS buffer"""
+        pipe, call = self.pipe, StageCall()
+        add_window_blend(call, logits.view(tiles.numel(), len(self.flips), len(ys), len(xs), self.K, self.S, self.S), ys, xs, self.flips, w1,
+                         self.mode, H, W, pipe.raw.shape[0], blend, mask, pipe.labels, tiles, pipe.lut, hist)
+        call.run()

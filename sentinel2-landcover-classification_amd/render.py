@@ -11,10 +11,8 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
 from .data import quicklook as QL
-from .plan import opdefs as D
-from .plan.program import Program, TRef
+from .stage_call import StageCall
 
 
 @torch.no_grad()
@@ -35,12 +33,8 @@ def overlay(base, classes: torch.Tensor, palette, alpha: float = 0.5, skip_zero:
     dev, K = classes.device, int(pal.shape[0])
     classes = classes.contiguous()
     out = torch.empty(B, SH, SW, 3, dtype=torch.uint8, device=dev)
-    prog = Program()
-    prog.add("CLASS_OVERLAY", CLS=TRef(D.BASE["X"], 0, (B, SH, SW), "i64"), PALETTE=TRef(D.BASE["CONST"], 0, (K, 3), "u8"),
-             BASE=None if base is None else TRef(D.BASE["Y"], 0, (B, SH, SW, 3), "u8"), OUT=TRef(D.BASE["OUT"], 0, (B, SH, SW, 3), "u8"),
-             B=B, SH=SH, SW=SW, K=K, ALPHA=a, SKIP0=int(bool(skip_zero)))
-    bases = _lib.Bases().set("X", classes).set("CONST", pal.to(dev)).set("OUT", out)
-    if base is not None:
-        bases.set("Y", base.contiguous())
-    _lib.run(prog.pack(), bases, torch.cuda.current_stream(dev).cuda_stream)
+    call = StageCall()
+    call.add("CLASS_OVERLAY", CLS=call.t(classes), PALETTE=call.t(pal.to(dev)), BASE=call.t(None if base is None else base.contiguous()),
+             OUT=call.t(out), B=B, SH=SH, SW=SW, K=K, ALPHA=a, SKIP0=int(bool(skip_zero)))
+    call.run()
     return out

@@ -16,11 +16,9 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch  # noqa: E402
 
 import s2lc_amd  # noqa: E402,F401
-from s2lc_amd import _lib  # noqa: E402
 from s2lc_amd import predict as P  # noqa: E402
 from s2lc_amd.data.gpu_pipeline import GpuTilePipeline  # noqa: E402
-from s2lc_amd.plan import opdefs as D  # noqa: E402
-from s2lc_amd.plan.program import Program, TRef  # noqa: E402
+from s2lc_amd.stage_call import StageCall  # noqa: E402
 
 H = W = 512
 S, STRIDE = 224, 112
@@ -40,34 +38,18 @@ def timed(fn, iters):
 
 
 def stage(logits, ys, xs, w1, mode, out, labels, index, lut):
-    """a callable that launches one WINDOW_BLEND over `logits` [M, 1, NY, NX, K, S, S] writing the output named `out`"""
+    """a callable that launches one WINDOW_BLEND (predict.add_window_blend) over `logits` [M, 1, NY, NX, K, S, S] writing the output
+    named `out`"""
     dev = logits.device
-    M, F, NY, NX, K = logits.shape[:5]
-    aux = torch.tensor(ys + xs + [0, 0, 0, 0], dtype=torch.int32, device=dev)
-    keep = {}
-    if out == "blend":
-        keep["OUT"] = torch.empty(M, K, H, W, dtype=torch.float32, device=dev)
-    elif out == "mask":
-        keep["DOUT"] = torch.empty(M, H, W, dtype=torch.int64, device=dev)
-    else:
-        keep["BUFS"] = torch.zeros(K, K, dtype=torch.int64, device=dev)
-    i32 = lambda off, n: TRef(D.BASE["AUX"], off, (n,), "i32")      # noqa: E731
-    hist = out == "hist"
-    prog = Program()
-    prog.add("WINDOW_BLEND", LOGITS=TRef(D.BASE["X"], 0, tuple(logits.shape)), YS=i32(0, NY), XS=i32(4 * NY, NX), FLIPS=i32(4 * (NY + NX), 1),
-             W1=TRef(D.BASE["CONST"], 0, (S,)), BLEND=TRef(D.BASE["OUT"], 0, (M, K, H, W)) if out == "blend" else None,
-             MASK=TRef(D.BASE["DOUT"], 0, (M, H, W), "i64") if out == "mask" else None,
-             LABELS=TRef(D.BASE["Y"], 0, tuple(labels.shape), "u8") if hist else None, INDEX=TRef(D.BASE["WGS"], 0, (M,), "i32") if hist else None,
-             LUT=TRef(D.BASE["NOISE"], 0, (256,), "i32") if hist else None, HIST=TRef(D.BASE["BUFS"], 0, (K, K), "i64") if hist else None,
-             M=M, F=F, NY=NY, NX=NX, K=K, H=H, W=W, S=S, NSRC=labels.shape[0], MODE=mode)
-    packed = prog.pack()
-    bases = _lib.Bases().set("X", logits).set("AUX", aux).set("CONST", w1)
-    for name, t in keep.items():
-        bases.set(name, t)
-    if hist:
-        bases.set("Y", labels).set("WGS", index).set("NOISE", lut)
+    M, K = logits.shape[0], logits.shape[4]
+    blend = torch.empty(M, K, H, W, dtype=torch.float32, device=dev) if out == "blend" else None
+    mask = torch.empty(M, H, W, dtype=torch.int64, device=dev) if out == "mask" else None
+    hist = torch.zeros(K, K, dtype=torch.int64, device=dev) if out == "hist" else None
+    call = StageCall()
+    P.add_window_blend(call, logits, ys, xs, [0], w1, mode, H, W, labels.shape[0], blend, mask, labels, index, lut, hist)
+    call.pack()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    return lambda: _lib.run(packed, bases, stream)
+    return lambda: call.run(stream)
 
 
 def torch_assembly(logits, ys, xs, w1, mode, out, labels, index, lut):
@@ -91,7 +73,7 @@ def torch_assembly(logits, ys, xs, w1, mode, out, labels, index, lut):
         mask = acc.argmax(dim=1)
         if out == "mask":
             return mask
-        t = lut.long()[labels[index.long()].long()]
+        t = lut.long()[labels[index.long().to(labels.device)].long()]
         ok = t < K
         return torch.bincount((t[ok] * K + mask[ok]), minlength=K * K)
 
@@ -121,7 +103,7 @@ def main():
             for m in range(M):
                 logits[m].normal_(0, 3, generator=g)
             labels = torch.randint(0, 24, (M, H, W), generator=g, device=dev, dtype=torch.uint8)
-            index = torch.arange(M, dtype=torch.int32, device=dev)
+            index = torch.arange(M, dtype=torch.int32)
             lut = (torch.arange(256, dtype=torch.int32) % 24 % K).to(dev)
             byts = logits.numel() * 4
             print(f"K = {K}: {M} tiles per launch, LOGITS {byts / 1e9:.3f} GB")

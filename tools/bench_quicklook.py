@@ -19,10 +19,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import s2lc_amd  # noqa: E402,F401
-from s2lc_amd import _lib  # noqa: E402
+from s2lc_amd.data import quicklook as QL  # noqa: E402
 from s2lc_amd.data.gpu_pipeline import GpuTilePipeline  # noqa: E402
-from s2lc_amd.plan import opdefs as D  # noqa: E402
-from s2lc_amd.plan.program import Program, TRef  # noqa: E402
+from s2lc_amd.stage_call import StageCall  # noqa: E402
 
 
 def timed(fn, iters):
@@ -91,16 +90,12 @@ def main():
     report(f"quicklook B={B} crops {S} (selection of {ntile} tiles + stretch)", ms, 2 * ntile * 3 * plane + B * S * S * 3 * 3, "moved")
     # the stretch stage alone, bounds given
     pct = torch.tensor([[100.0, 3000.0]] * B, dtype=torch.float64, device=dev)
-    aux = torch.cat([par.reshape(-1), torch.arange(B, dtype=torch.int32), torch.tensor(rgb + (0,), dtype=torch.int32)]).to(dev)
     out = torch.empty(B, S, S, 3, dtype=torch.uint8, device=dev)
-    prog = Program()
-    prog.add("TILE_QUICKLOOK", RAW=TRef(D.BASE["X"], 0, (N, C, H, H), "i16"), PARAMS=TRef(D.BASE["AUX"], 0, (B, 4), "i32"),
-             SLOT=TRef(D.BASE["AUX"], 16 * B, (B,), "i32"), BANDS=TRef(D.BASE["AUX"], 20 * B, (3,), "i32"),
-             PCT=TRef(D.BASE["CONST"], 0, (B, 2), "f64"), OUT=TRef(D.BASE["OUT"], 0, (B, S, S, 3), "u8"),
-             B=B, C=C, H=H, W=H, SH=S, SW=S, NSRC=N, NROW=B, NQ=2)
-    packed, bases = prog.pack(), _lib.Bases().set("X", raw).set("AUX", aux).set("CONST", pct).set("OUT", out)
+    call = StageCall()
+    QL.add_quicklook(call, raw, par, torch.arange(B, dtype=torch.int32), rgb, call.t(pct), out, B)
+    call.pack()
     stream = torch.cuda.current_stream().cuda_stream
-    report(f"TILE_QUICKLOOK stage alone, B={B} crops {S}", timed(lambda: _lib.run(packed, bases, stream), a.iters), B * S * S * 3 * (2 + 1), "moved")
+    report(f"TILE_QUICKLOOK stage alone, B={B} crops {S}", timed(lambda: call.run(stream), a.iters), B * S * S * 3 * (2 + 1), "moved")
     byts = B * S * S * C * (2 + 4)
     ms = timed(lambda: pipe(params=par), a.iters)
     report(f"TILE_PREP B={B} (yardstick, read + written)", ms, byts, "moved")
