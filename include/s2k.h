@@ -89,6 +89,9 @@ int s2k_program_profile_ops(const S2kOp* ops, int begin, int end, void* const* b
  * dwconv_{fwd,dgrad}_plane_s2_kernel), 7 for dwconv_wgrad_kernel walking images inside the workgroup (its image loop).
  * ViT stages: CHAN_LN_FWD 0 for the tile kernel (chan_ln_fwd_kernel), 8 for the row kernel (chan_ln_fwd_rows_kernel);
  * MAE_LOSS_FWD / _BWD 0 for the float4 form of mae_loss_rows_kernel (<*, true>), 9 for its scalar form (<*, false>).
+ * 10 on all four records of a small-plane depthwise backward chain (BN_BWD_APPLY flagged S2K_FLAG_CHAIN, DWCONV_WGRAD,
+ * DWCONV_DGRAD, BN_BWD_APPLY) that ran as ONE kernel (dw_bwd_chain_kernel): its time is reported on the first record, the other
+ * three report 0 ms and no launch.
  * bench.py uses it to attribute time and algorithmic FLOPs to the kernel names a rocprofv3 trace shows. */
 int s2k_program_profile_variants(const S2kOp* ops, int begin, int end, void* const* bases, int n_bases, void* stream,
                                  float* ms_per_op, int* variant_per_op);

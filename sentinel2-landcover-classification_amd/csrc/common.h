@@ -261,6 +261,44 @@ __device__ __forceinline__ void bn_fold_wave(const BnFold& f, int C, int c, bool
     bn_fold_finish(f, C, c, s, q, writer && lane == 0, scale, shift);
 }
 
+// ---- BN_BWD_FINALIZE folded into its consumer -----------------------------------------------------
+// the per-channel work of BN_BWD_FINALIZE done by the consumer: sums of g' and g'*xhat over the replicas -> coefficients;
+// the wave that owns the first chunk of sample 0 publishes the parameter gradients
+struct BnFuse {
+    const double* st2;
+    const float* gamma;
+    float *dgamma, *dbeta;
+    double inv_count;
+    int nrep;
+    const float *mulbc, *addbc;   // MODE 3: g' = (GP * mul + add * addscale) * silu'(u) is recomputed here
+    float addscale;
+    const float* ps;              // MODE 3: SE_BN_SUMS's plane sums [4][B][C]; the sums over the batch are formed here (SE_BN_COMBINE)
+    int B;
+};
+
+// the channel's two BN-backward sums: from the STATS2 replicas, or (fz.ps) combined from the SE backward's plane sums - the same
+// lane order in every wave, so all waves of a channel agree bit for bit
+__device__ __forceinline__ void bn_fuse_sums(const BnFuse& fz, int C, int c, int lane, double& s1, double& s2) {
+    s1 = 0.0; s2 = 0.0;
+    if (fz.ps) {
+        const int64_t np = (int64_t)fz.B * C;
+        for (int b = lane; b < fz.B; b += 64) {
+            const int64_t pl = (int64_t)b * C + c;
+            const double mul = fz.mulbc ? (double)fz.mulbc[pl] : 1.0, add = fz.addbc ? (double)fz.addbc[pl] * (double)fz.addscale : 0.0;
+            s1 += mul * (double)fz.ps[pl] + add * (double)fz.ps[np + pl];
+            s2 += mul * (double)fz.ps[2 * np + pl] + add * (double)fz.ps[3 * np + pl];
+        }
+        s1 = wave_sum_d(s1);
+        s2 = wave_sum_d(s2);
+    } else if (fz.nrep <= 8) {   // wave-uniform addresses: scalar loads
+        for (int r = 0; r < fz.nrep; ++r) { s1 += fz.st2[(int64_t)r * 2 * C + c]; s2 += fz.st2[(int64_t)r * 2 * C + C + c]; }
+    } else {
+        for (int r = lane; r < fz.nrep; r += 64) { s1 += fz.st2[(int64_t)r * 2 * C + c]; s2 += fz.st2[(int64_t)r * 2 * C + C + c]; }
+        s1 = wave_sum_d(s1);
+        s2 = wave_sum_d(s2);
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 
@@ -280,7 +318,8 @@ inline int tune_int(const char* name, int dflt) {
 // 1 = the producer/consumer kernel (conv_pc_kernel / wgrad_pc_kernel), 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads, 5 f32-split;
 // depthwise stages: 0 = the band kernels, 6 = the wave-per-channel plane kernels (dwconv_*_plane_kernel, dwconv_*_plane_s2_kernel),
 // 7 = dwconv_wgrad_kernel's image loop (bloop > 0); ViT stages: 8 = chan_ln_fwd_rows_kernel (0 = the tile kernel), 9 = the scalar
-// form of mae_loss_rows_kernel (0 = its float4 form).  The full list is in include/s2k.h.
+// form of mae_loss_rows_kernel (0 = its float4 form); 10 = all four records of a depthwise backward chain run as one dw_bwd_chain_kernel.
+// The full list is in include/s2k.h.
 extern thread_local int g_s2k_variant;
 
 // hipFuncSetAttribute acts on the current device: run a kernel's attribute call once per device.  std::call_once makes every

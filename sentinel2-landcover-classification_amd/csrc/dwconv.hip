@@ -1075,6 +1075,194 @@ __global__ void __launch_bounds__(NTHREADS) dwconv_dgrad_plane_kernel(const DwP 
     }
 }
 
+// ---- the small-plane depthwise backward chain as one kernel (8 x 8 and 16 x 16 planes, stride 1) ----------------------------------------
+// Four records of an MBConv block's backward walk the same expanded tensor one after the other (plan/opdefs.py FLAG_CHAIN):
+//   BN_BWD_APPLY (depthwise BatchNorm, g' recomputed from the SE backward's plane sums)      dy1 = k0 g1 + k1 y_dw + k2
+//   DWCONV_WGRAD                                                                             DW += sum dy1 * a(shifted), a = silu(bn_exp(x_exp))
+//   DWCONV_DGRAD (PRO = SiLU, writes g' of the expand BatchNorm and its two sums)            g2 = (dy1 * flipped w) silu'(bn_exp(x_exp))
+//   BN_BWD_APPLY (expand BatchNorm)                                                          G = k0' g2 + k1' x_exp + k2'
+// = 11 passes over HBM and 4 launches, although every step is per channel - the batch-wide sums of train-mode BatchNorm included.
+// Here ONE WORKGROUP owns a channel: its 4 waves split the batch (a wave takes one 16 x 16 plane or four 8 x 8 planes per pass, the
+// next pass's three 16-byte loads always in flight), dy1 and a go through wave-private LDS tiles with a zero halo exactly as in the plane
+// kernels above, the K * K tap sums and the two BatchNorm sums stay in registers (f32 per lane, combined in f64), g2 is stored to G.
+// After ONE workgroup barrier the sums are combined through LDS, DW / DGAMMA / DBETA of both BatchNorms receive their += (this
+// workgroup is the only writer of the channel: no atomics, no replicas), and every lane re-reads the g2 values IT stored (a thread's
+// own stores are visible to it in program order; they come back from L2) beside x_exp and writes k0' g2 + k1' x_exp + k2' in place.
+// d, y_dw and x_exp are read once (x_exp a second time from cache); dy1 is written in place over d, as the first record does (every
+// tensor of the plan holds what the four stages would have left, only the data gradient's STATS2 is not written), and G once with g2 and
+// once with the result.  Loads never sit under a condition: images past the end of the batch are clamped to the last one and their
+// values discarded (a clamped lane may read an element of d that its owner has already overwritten with dy1: discarded as well).
+struct DwChainP {
+    const float *d, *ydw, *bnv1, *mulbc, *addbc, *ps, *gamma1;     // depthwise BatchNorm: upstream gradient, raw output, {scale, shift, mean, invstd}, SE terms
+    float *dy, *dgamma1, *dbeta1;                                  // dy == d: the record applies in place
+    const float *x, *bnv2, *w, *gamma2;                            // expand conv's raw output and its BatchNorm, depthwise weights [C][K][K]
+    float *dw, *g, *dgamma2, *dbeta2;
+    double inv_count1, inv_count2;
+    float addscale;
+    int B, C;
+};
+
+template <int K, int W>
+__global__ void __launch_bounds__(NTHREADS) dw_bwd_chain_kernel(const DwChainP p) {
+    constexpr int PADK = (K - 1) / 2, KK = K * K;
+    constexpr int GPP = W * W / 4, LPP = GPP > 64 ? 64 : GPP, PW = 64 / LPP, XGW = W / 4;
+    constexpr int TH = W + K - 1, TW = W + 8, TILE = TH * TW, HW = W * W;
+    constexpr int WAVE_TILES = 2 * 2 * PW * TILE;                     // [2 buffers][dy1 | a][PW][TILE]
+    static_assert(GPP == 64 || GPP == 16, "8 x 8 or 16 x 16 planes");
+    static_assert((4 * WAVE_TILES) % 4 == 0, "the reduction scratch behind the tiles stays 16-byte aligned");
+    extern __shared__ __attribute__((aligned(16))) float smem[];     // [4 waves][WAVE_TILES] | double red_s[4][2] | float red_t[4][KK]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.x;
+    const int B = p.B, C = p.C;
+    const int sub = lane / LPP, li = lane % LPP;
+    const int r = li / XGW, xg = li % XGW;
+    const int64_t bstride = (int64_t)C * HW;
+    const int64_t loff = (int64_t)c * HW + 4 * li;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    // this lane's images: b = wave * PW + sub, then every 4 * PW further; the first pass's loads go out before anything else
+    const int b_first = wave * PW + sub;
+    f32x4 dcur, ycur, xcur;
+    float mcur, acur;
+    {
+        const int bc = min(b_first, B - 1);
+        const int64_t off = (int64_t)bc * bstride + loff;
+        dcur = *reinterpret_cast<const f32x4*>(p.d + off);
+        ycur = *reinterpret_cast<const f32x4*>(p.ydw + off);
+        xcur = *reinterpret_cast<const f32x4*>(p.x + off);
+        mcur = p.mulbc[(int64_t)bc * C + c];
+        acur = p.addbc[(int64_t)bc * C + c];
+    }
+    // depthwise BatchNorm: coefficients of dy1 = k0 g1 + k1 y + k2, formed as plane_map_kernel<3> forms them (every wave for itself:
+    // the same lane order, so the four waves agree bit for bit)
+    BnFuse fz{};
+    fz.mulbc = p.mulbc; fz.addbc = p.addbc; fz.addscale = p.addscale; fz.ps = p.ps; fz.B = B;
+    double s1d, s2d;
+    bn_fuse_sums(fz, C, c, lane, s1d, s2d);
+    const float bscale1 = p.bnv1[c], bshift1 = p.bnv1[C + c];
+    float k0, k1, k2;
+    {
+        const float mean = p.bnv1[2 * C + c], invstd = p.bnv1[3 * C + c];
+        const double aa = (double)p.gamma1[c] * (double)invstd;
+        const float A = (float)aa, Bq = (float)(-aa * s2d * p.inv_count1), Cq = (float)(-aa * s1d * p.inv_count1);
+        k0 = A; k1 = Bq * invstd; k2 = Cq - Bq * invstd * mean;
+        if (threadIdx.x == 0) {
+            p.dgamma1[c] += (float)s2d;
+            p.dbeta1[c] += (float)s1d;
+        }
+    }
+    const float scale2 = p.bnv2[c], shift2 = p.bnv2[C + c], mean2 = p.bnv2[2 * C + c], invstd2 = p.bnv2[3 * C + c];
+    float wk[KK];
+#pragma unroll
+    for (int i = 0; i < KK; ++i) wk[i] = p.w[c * KK + (KK - 1 - i)];        // flipped (the data gradient)
+    float* tiles = smem + wave * WAVE_TILES;
+    for (int i = lane; i < WAVE_TILES / 4; i += 64) reinterpret_cast<f32x4*>(tiles)[i] = zero;
+    float acc[KK];
+#pragma unroll
+    for (int i = 0; i < KK; ++i) acc[i] = 0.0f;
+    float s1 = 0.0f, s2 = 0.0f;
+    int buf = 0;
+    for (int b = b_first; b - sub < B; b += 4 * PW, buf ^= 1) {             // (b - sub is wave-uniform: all lanes of a wave leave together)
+        const bool ok = b < B;
+        f32x4 dnxt, ynxt, xnxt;
+        float mnxt, anxt;
+        {
+            const int bc = min(b + 4 * PW, B - 1);
+            const int64_t off = (int64_t)bc * bstride + loff;
+            dnxt = *reinterpret_cast<const f32x4*>(p.d + off);              // in flight during this pass
+            ynxt = *reinterpret_cast<const f32x4*>(p.ydw + off);
+            xnxt = *reinterpret_cast<const f32x4*>(p.x + off);
+            mnxt = p.mulbc[(int64_t)bc * C + c];
+            anxt = p.addbc[(int64_t)bc * C + c];
+        }
+        const float gadd = acur * p.addscale;
+        f32x4 dy1, av;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float g1 = fmaf(dcur[j], mcur, gadd) * act_grad(fmaf(ycur[j], bscale1, bshift1), S2K_PRO_SILU);
+            dy1[j] = fmaf(k0, g1, fmaf(k1, ycur[j], k2));
+            av[j] = apply_pro_c<S2K_PRO_SILU>(xcur[j], scale2, shift2);
+        }
+        if (!ok) { dy1 = zero; av = zero; }
+        else *reinterpret_cast<f32x4*>(p.dy + (int64_t)b * bstride + loff) = dy1;      // the depthwise BatchNorm's dY, in place over d
+        float* td = tiles + ((buf * 2 + 0) * PW + sub) * TILE;
+        float* ta = tiles + ((buf * 2 + 1) * PW + sub) * TILE;
+        *reinterpret_cast<f32x4*>(td + (r + PADK) * TW + 4 + 4 * xg) = dy1;
+        *reinterpret_cast<f32x4*>(ta + (r + PADK) * TW + 4 + 4 * xg) = av;
+        __builtin_amdgcn_wave_barrier();
+        float o[4] = {0.f, 0.f, 0.f, 0.f};
+        const float* d0 = td + r * TW + 4 * xg;       // rows r .. r + K - 1, tile columns 4 xg .. 4 xg + 11 = image columns 4 xg - 4 ..
+        const float* a0 = ta + r * TW + 4 * xg;
+#pragma unroll
+        for (int ky = 0; ky < K; ++ky) {
+            float win[12];
+            read_window<3>(a0 + ky * TW, win);
+#pragma unroll
+            for (int kx = 0; kx < K; ++kx)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[ky * K + kx] = fmaf(dy1[j], win[4 - PADK + j + kx], acc[ky * K + kx]);
+            read_window<3>(d0 + ky * TW, win);
+#pragma unroll
+            for (int kx = 0; kx < K; ++kx)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = fmaf(wk[ky * K + kx], win[4 - PADK + j + kx], o[j]);
+        }
+        if (ok) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] *= act_grad(fmaf(xcur[j], scale2, shift2), S2K_PRO_SILU);
+                s1 += o[j];
+                s2 = fmaf(o[j], (xcur[j] - mean2) * invstd2, s2);
+            }
+            *reinterpret_cast<f32x4*>(p.g + (int64_t)b * bstride + loff) = f32x4{o[0], o[1], o[2], o[3]};
+        }
+        dcur = dnxt; ycur = ynxt; xcur = xnxt; mcur = mnxt; acur = anxt;
+    }
+    // combine the four waves' sums
+    double* red_s = reinterpret_cast<double*>(smem + 4 * WAVE_TILES);        // [4][2]
+    float* red_t = smem + 4 * WAVE_TILES + 16;                               // [4][KK]
+    {
+        const double sd = wave_sum_d((double)s1), qd = wave_sum_d((double)s2);
+        if (lane == 0) { red_s[wave * 2] = sd; red_s[wave * 2 + 1] = qd; }
+#pragma unroll
+        for (int i = 0; i < KK; ++i) {
+            const float v = wave_sum(acc[i]);
+            if (lane == 0) red_t[wave * KK + i] = v;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < KK) p.dw[c * KK + threadIdx.x] += (red_t[threadIdx.x] + red_t[KK + threadIdx.x]) + (red_t[2 * KK + threadIdx.x] + red_t[3 * KK + threadIdx.x]);
+    // expand BatchNorm: every thread forms the same three coefficients from the same four partial sums
+    {
+        const double t1 = (red_s[0] + red_s[2]) + (red_s[4] + red_s[6]), t2 = (red_s[1] + red_s[3]) + (red_s[5] + red_s[7]);
+        const double aa = (double)p.gamma2[c] * (double)invstd2;
+        const float A = (float)aa, Bq = (float)(-aa * t2 * p.inv_count2), Cq = (float)(-aa * t1 * p.inv_count2);
+        k0 = A; k1 = Bq * invstd2; k2 = Cq - Bq * invstd2 * mean2;
+        if (threadIdx.x == 0) {
+            p.dgamma2[c] += (float)t2;
+            p.dbeta2[c] += (float)t1;
+        }
+    }
+    // last phase: G = k0 g2 + k1 x_exp + k2 in place, every lane over the elements it stored itself (two images in flight)
+    for (int b = b_first; b - sub < B; b += 8 * PW) {
+        const int b1 = b + 4 * PW;
+        const int64_t off0 = (int64_t)min(b, B - 1) * bstride + loff, off1 = (int64_t)min(b1, B - 1) * bstride + loff;
+        const f32x4 g0 = *reinterpret_cast<const f32x4*>(p.g + off0), x0 = *reinterpret_cast<const f32x4*>(p.x + off0);
+        const f32x4 g1 = *reinterpret_cast<const f32x4*>(p.g + off1), x1 = *reinterpret_cast<const f32x4*>(p.x + off1);
+        if (b < B) {
+            f32x4 v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = fmaf(k0, g0[j], fmaf(k1, x0[j], k2));
+            *reinterpret_cast<f32x4*>(p.g + off0) = v;
+        }
+        if (b1 < B) {
+            f32x4 v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = fmaf(k0, g1[j], fmaf(k1, x1[j], k2));
+            *reinterpret_cast<f32x4*>(p.g + off1) = v;
+        }
+    }
+}
+
 // ---- data gradient at stride 2 on even square planes: the wave-per-channel scheme --------------------------------------------------
 // A lane owns one 4-pixel group of dY (row r, columns 4 xg ..) and computes the 2 x 8 input pixels below it (rows 2r, 2r + 1, columns
 // 8 xg .. 8 xg + 7): input pixel (2r + py, 8 xg + 2q + px) only meets the taps with ky = (py + PT) mod 2, kx = (px + PL) mod 2 - every tap
@@ -1607,6 +1795,53 @@ int launch_dwconv_dgrad(const S2kOp& op, const Ctx& c) {
     }
     const size_t lds = tile_rows(p, p.H, p.W, irt_dgrad2, p.WO + 2, true, false);   // one zero column on either side
     return p.K == 3 ? launch_dw(dwconv_dgrad_s2_kernel<3>, p, lds, c.stream) : launch_dw(dwconv_dgrad_s2_kernel<5>, p, lds, c.stream);
+}
+
+// The four records o[0 .. 3] of a depthwise backward chain as one kernel.  The executor (s2k_api.hip, try_dw_chain) has checked the
+// pattern: kinds, matching tensor references, stride 1, W = H in {8, 16}, K in {3, 5}, train-mode, f32 in place.
+int launch_dw_bwd_chain(const S2kOp* o, const Ctx& c) {
+    const S2kOp &a1 = o[0], &wg = o[1], &dg = o[2], &a2 = o[3];
+    DwChainP p{};
+    p.d = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_GP]);
+    p.dy = ref_ptr<float>(c, a1.t[S2K_BN_BWD_APPLY_T_DY]);
+    p.ydw = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_Y]);
+    p.bnv1 = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_BNV]);
+    p.mulbc = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_MULBC]);
+    p.addbc = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_ADDBC]);
+    p.ps = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_PS]);
+    p.gamma1 = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_GAMMA]);
+    p.dgamma1 = ref_ptr<float>(c, a1.t[S2K_BN_BWD_APPLY_T_DGAMMA]);
+    p.dbeta1 = ref_ptr<float>(c, a1.t[S2K_BN_BWD_APPLY_T_DBETA]);
+    p.x = ref_ptr<const float>(c, dg.t[S2K_DWCONV_DGRAD_T_XRAW]);
+    p.bnv2 = ref_ptr<const float>(c, dg.t[S2K_DWCONV_DGRAD_T_BNV]);
+    p.w = ref_ptr<const float>(c, dg.t[S2K_DWCONV_DGRAD_T_WT]);
+    p.dw = ref_ptr<float>(c, wg.t[S2K_DWCONV_WGRAD_T_DW]);
+    p.g = ref_ptr<float>(c, dg.t[S2K_DWCONV_DGRAD_T_G]);
+    p.gamma2 = ref_ptr<const float>(c, a2.t[S2K_BN_BWD_APPLY_T_GAMMA]);
+    p.dgamma2 = ref_ptr<float>(c, a2.t[S2K_BN_BWD_APPLY_T_DGAMMA]);
+    p.dbeta2 = ref_ptr<float>(c, a2.t[S2K_BN_BWD_APPLY_T_DBETA]);
+    const void* all[] = {p.d, p.dy, p.ydw, p.bnv1, p.mulbc, p.addbc, p.ps, p.gamma1, p.dgamma1, p.dbeta1, p.x, p.bnv2, p.w, p.dw, p.g, p.gamma2,
+                         p.dgamma2, p.dbeta2};
+    for (const void* q : all) {
+        if (bad(q)) { set_error("dw_bwd_chain: null base"); return S2K_EFAULT; }
+        if (!q) { set_error("dw_bwd_chain: missing tensor"); return S2K_EINVAL; }
+    }
+    p.B = dg.d[0]; p.C = dg.d[1];
+    const int W = dg.d[3], K = dg.d[4];
+    p.inv_count1 = 1.0 / (double)a1.n[S2K_BN_BWD_APPLY_N_COUNT];
+    p.inv_count2 = 1.0 / (double)a2.n[S2K_BN_BWD_APPLY_N_COUNT];
+    p.addscale = a1.f[S2K_BN_BWD_APPLY_F_ADDSCALE];
+    const int pw = W == 8 ? 4 : 1;
+    const size_t lds = ((size_t)4 * 2 * 2 * pw * (W + K - 1) * (W + 8) + 16 + 4 * K * K) * sizeof(float);
+    if (lds > 64 * 1024) { set_error("dw_bwd_chain: tile too large (%zu B)", lds); return S2K_EINVAL; }
+    const dim3 grid(p.C);
+    if (K == 3 && W == 8) hipLaunchKernelGGL((dw_bwd_chain_kernel<3, 8>), grid, dim3(NTHREADS), lds, c.stream, p);
+    else if (K == 3 && W == 16) hipLaunchKernelGGL((dw_bwd_chain_kernel<3, 16>), grid, dim3(NTHREADS), lds, c.stream, p);
+    else if (K == 5 && W == 8) hipLaunchKernelGGL((dw_bwd_chain_kernel<5, 8>), grid, dim3(NTHREADS), lds, c.stream, p);
+    else if (K == 5 && W == 16) hipLaunchKernelGGL((dw_bwd_chain_kernel<5, 16>), grid, dim3(NTHREADS), lds, c.stream, p);
+    else { set_error("dw_bwd_chain: unsupported plane %d, k %d", W, K); return S2K_EINVAL; }
+    g_s2k_variant = 10;
+    return S2K_OK;
 }
 
 }  // namespace s2k

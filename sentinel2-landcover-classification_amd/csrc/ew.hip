@@ -1243,43 +1243,8 @@ int launch_bn_bwd_finalize(const S2kOp& op, const Ctx& c) {
     return S2K_OK;
 }
 
-// the per-channel work of BN_BWD_FINALIZE done by the consumer: sums of g' and g'*xhat over the replicas -> coefficients;
-// the wave that owns the first chunk of sample 0 publishes the parameter gradients
-struct BnFuse {
-    const double* st2;
-    const float* gamma;
-    float *dgamma, *dbeta;
-    double inv_count;
-    int nrep;
-    const float *mulbc, *addbc;   // MODE 3: g' = (GP * mul + add * addscale) * silu'(u) is recomputed here
-    float addscale;
-    const float* ps;              // MODE 3: SE_BN_SUMS's plane sums [4][B][C]; the sums over the batch are formed here (SE_BN_COMBINE)
-    int B;
-};
-
-// the channel's two BN-backward sums: from the STATS2 replicas, or (fz.ps) combined from the SE backward's plane sums - the same
-// lane order in every wave, so all waves of a channel agree bit for bit
-__device__ __forceinline__ void bn_fuse_sums(const BnFuse& fz, int C, int c, int lane, double& s1, double& s2) {
-    s1 = 0.0; s2 = 0.0;
-    if (fz.ps) {
-        const int64_t np = (int64_t)fz.B * C;
-        for (int b = lane; b < fz.B; b += 64) {
-            const int64_t pl = (int64_t)b * C + c;
-            const double mul = fz.mulbc ? (double)fz.mulbc[pl] : 1.0, add = fz.addbc ? (double)fz.addbc[pl] * (double)fz.addscale : 0.0;
-            s1 += mul * (double)fz.ps[pl] + add * (double)fz.ps[np + pl];
-            s2 += mul * (double)fz.ps[2 * np + pl] + add * (double)fz.ps[3 * np + pl];
-        }
-        s1 = wave_sum_d(s1);
-        s2 = wave_sum_d(s2);
-    } else if (fz.nrep <= 8) {   // wave-uniform addresses: scalar loads
-        for (int r = 0; r < fz.nrep; ++r) { s1 += fz.st2[(int64_t)r * 2 * C + c]; s2 += fz.st2[(int64_t)r * 2 * C + C + c]; }
-    } else {
-        for (int r = lane; r < fz.nrep; r += 64) { s1 += fz.st2[(int64_t)r * 2 * C + c]; s2 += fz.st2[(int64_t)r * 2 * C + C + c]; }
-        s1 = wave_sum_d(s1);
-        s2 = wave_sum_d(s2);
-    }
-}
-
+// (BnFuse / bn_fuse_sums - the per-channel work of BN_BWD_FINALIZE done by the consumer - live in common.h: dwconv.hip's chain kernel
+// forms the same sums)
 // MODE 0: dy = A*gp + Bq*xhat + Cq (BN_BWD_APPLY; MODE 2 = the same with the coefficients computed here from STATS2;
 // MODE 3 = MODE 2 with gp = (a*mul + add) * silu'(scale*y + shift) recomputed per element, see SE_BN_SUMS);
 // MODE 1: xout = (scale*y+shift)*dcs[b] + ident (BN_RESIDUAL)

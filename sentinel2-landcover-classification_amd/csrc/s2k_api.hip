@@ -81,6 +81,7 @@ int launch_tile_radix_hist(const S2kOp&, const Ctx&);
 int launch_tile_rank_pick(const S2kOp&, const Ctx&);
 int launch_tile_quicklook(const S2kOp&, const Ctx&);
 int launch_class_overlay(const S2kOp&, const Ctx&);
+int launch_dw_bwd_chain(const S2kOp*, const Ctx&);
 int launch_adam(float*, const float*, float*, float*, int64_t, double, double, double, double, double, int, hipStream_t);
 int launch_mfma_selftest(const float*, const float*, float*, hipStream_t);
 
@@ -269,6 +270,45 @@ struct DeviceGuard {
     }
 };
 
+// A depthwise backward chain (plan/opdefs.py FLAG_CHAIN) starts at ops[i]: BN_BWD_APPLY (depthwise BatchNorm, recomputing form) ->
+// DWCONV_WGRAD -> DWCONV_DGRAD (SiLU, statistics) -> BN_BWD_APPLY (expand BatchNorm) over one expanded tensor.  The flag is a
+// permission, not an order: the pattern and the shapes are checked again here, and whatever does not fit runs record by record
+// as if the flag were not there.  Returns the number of records consumed: 4 (one launch of dw_bwd_chain_kernel on c.stream, *rc
+// its status) or 0 (declined: nothing was launched).
+static int try_dw_chain(const S2kOp* ops, int i, int end, const Ctx& c, int* rc) {
+    if (!(ops[i].flags & S2K_FLAG_CHAIN) || i + 3 >= end) return 0;
+    const S2kOp &a1 = ops[i], &wg = ops[i + 1], &dg = ops[i + 2], &a2 = ops[i + 3];
+    if (a1.kind != S2K_OP_BN_BWD_APPLY || wg.kind != S2K_OP_DWCONV_WGRAD || dg.kind != S2K_OP_DWCONV_DGRAD || a2.kind != S2K_OP_BN_BWD_APPLY) return 0;
+    if ((a1.flags | wg.flags | dg.flags | a2.flags) & (S2K_FLAG_BF16 | S2K_FLAG_SPLIT)) return 0;
+    const int64_t dy = a1.t[S2K_BN_BWD_APPLY_T_DY], x = dg.t[S2K_DWCONV_DGRAD_T_XRAW], g = dg.t[S2K_DWCONV_DGRAD_T_G];
+    // first APPLY: SiLU, g' recomputed from the SE backward's plane sums, train mode, f32 in place
+    if (dy < 0 || a1.t[S2K_BN_BWD_APPLY_T_GP] != dy || a1.t[S2K_BN_BWD_APPLY_T_COEF] >= 0 || a1.t[S2K_BN_BWD_APPLY_T_PS] < 0 ||
+        a1.t[S2K_BN_BWD_APPLY_T_MULBC] < 0 || a1.t[S2K_BN_BWD_APPLY_T_ADDBC] < 0 || a1.d[S2K_BN_BWD_APPLY_D_ACT] != S2K_PRO_SILU ||
+        a1.d[S2K_BN_BWD_APPLY_D_EVAL] || a1.d[S2K_BN_BWD_APPLY_D_OUT_BF16] || a1.n[S2K_BN_BWD_APPLY_N_COUNT] <= 0) return 0;
+    // the two depthwise gradients read that dY and the same expanded activation
+    if (wg.t[S2K_DWCONV_WGRAD_T_DY] != dy || dg.t[S2K_DWCONV_DGRAD_T_DY] != dy || x < 0 || wg.t[S2K_DWCONV_WGRAD_T_X] != x ||
+        dg.t[S2K_DWCONV_DGRAD_T_BNV] < 0 || wg.t[S2K_DWCONV_WGRAD_T_BNV] != dg.t[S2K_DWCONV_DGRAD_T_BNV] || g < 0 || g == dy || g == x ||
+        dg.t[S2K_DWCONV_DGRAD_T_STATS2] < 0) return 0;
+    for (int k = 0; k <= 10; ++k)          // B, C, H, W, K, STRIDE, PAD_T, PAD_L, HO, WO, PRO: the same slots in both records
+        if (wg.d[k] != dg.d[k]) return 0;
+    const int B = dg.d[0], C = dg.d[1], H = dg.d[2], W = dg.d[3], K = dg.d[4];
+    if (B <= 0 || C <= 0 || H != W || (W != 8 && W != 16) || (K != 3 && K != 5) || dg.d[5] != 1 || dg.d[6] != (K - 1) / 2 || dg.d[7] != (K - 1) / 2 ||
+        dg.d[8] != H || dg.d[9] != W || dg.d[10] != S2K_PRO_SILU || dg.d[S2K_DWCONV_DGRAD_D_BETA] != 0) return 0;
+    if ((int64_t)B * C * H * W * 4 >= 0x7ffffff0ll) return 0;
+    // second APPLY: the plain fused form, in place on the data gradient, with the sums the data gradient would have written
+    if (a2.t[S2K_BN_BWD_APPLY_T_GP] != g || a2.t[S2K_BN_BWD_APPLY_T_DY] != g || a2.t[S2K_BN_BWD_APPLY_T_Y] != x ||
+        a2.t[S2K_BN_BWD_APPLY_T_BNV] != dg.t[S2K_DWCONV_DGRAD_T_BNV] || a2.t[S2K_BN_BWD_APPLY_T_STATS2] != dg.t[S2K_DWCONV_DGRAD_T_STATS2] ||
+        a2.t[S2K_BN_BWD_APPLY_T_COEF] >= 0 || a2.t[S2K_BN_BWD_APPLY_T_PS] >= 0 || a2.t[S2K_BN_BWD_APPLY_T_MULBC] >= 0 ||
+        a2.t[S2K_BN_BWD_APPLY_T_ADDBC] >= 0 || a2.d[S2K_BN_BWD_APPLY_D_ACT] != S2K_PRO_NONE || a2.d[S2K_BN_BWD_APPLY_D_EVAL] ||
+        a2.d[S2K_BN_BWD_APPLY_D_OUT_BF16] || a2.n[S2K_BN_BWD_APPLY_N_COUNT] <= 0) return 0;
+    const int HW = H * W;
+    if (a1.d[S2K_BN_BWD_APPLY_D_B] != B || a1.d[S2K_BN_BWD_APPLY_D_C] != C || a1.d[S2K_BN_BWD_APPLY_D_HW] != HW ||
+        a2.d[S2K_BN_BWD_APPLY_D_B] != B || a2.d[S2K_BN_BWD_APPLY_D_C] != C || a2.d[S2K_BN_BWD_APPLY_D_HW] != HW) return 0;
+    g_s2k_variant = 0;
+    *rc = check_launch(launch_dw_bwd_chain(&ops[i], c), ops[i], i);
+    return 4;
+}
+
 int s2k_program_run(const S2kOp* ops, int begin, int end, void* const* bases, int n_bases, void* stream) {
     if (!ops || !bases || begin < 0 || end < begin) { set_error("program_run: bad arguments"); return S2K_EINVAL; }
     hipStream_t main_st = static_cast<hipStream_t>(stream);
@@ -288,6 +328,18 @@ int s2k_program_run(const S2kOp* ops, int begin, int end, void* const* bases, in
     int rc = S2K_OK;
     for (int i = begin; i < end; ++i) {
         const S2kOp& op = ops[i];
+        if ((op.flags & S2K_FLAG_CHAIN) && i + 3 < end) {
+            // a join asked for by any record of the chain is honoured in front of it (merely early if the chain is then declined); the
+            // consumed DWCONV_WGRAD is not issued to the side stream
+            if ((op.flags | ops[i + 1].flags | ops[i + 2].flags | ops[i + 3].flags) & S2K_FLAG_JOIN) join();
+            const int used = try_dw_chain(ops, i, end, c, &rc);
+            if (used) {
+                main_dirty = true;
+                if (rc != S2K_OK) break;
+                i += used - 1;
+                continue;
+            }
+        }
         if ((op.flags & S2K_FLAG_SIDE) && sq) {
             if (main_dirty) {
                 (void)hipEventRecord(sq->fork, main_st);
@@ -354,12 +406,18 @@ static int profile_impl(const S2kOp* ops, int begin, int end, void* const* bases
     int rc = S2K_OK;
     hipEventRecord(ev[0], st);
     int done = 0;
+    std::vector<char> fused(n, 0);      // records consumed by the launch of an earlier one: 0 ms, no launch of their own
     for (int i = 0; i < n; ++i) {
         g_s2k_variant = 0;
-        rc = check_launch(dispatch(ops[begin + i], c), ops[begin + i], begin + i);
+        const int used = try_dw_chain(ops, begin + i, end, c, &rc);
+        if (!used) rc = check_launch(dispatch(ops[begin + i], c), ops[begin + i], begin + i);
         if (rc != S2K_OK) break;
-        if (variant_per_op) variant_per_op[i] = g_s2k_variant;
-        hipEventRecord(ev[i + 1], st);
+        for (int k = 0; k < (used ? used : 1); ++k) {
+            if (variant_per_op) variant_per_op[i + k] = g_s2k_variant;
+            hipEventRecord(ev[i + k + 1], st);
+            if (k) fused[i + k] = 1;
+        }
+        if (used) i += used - 1;
         done = i + 1;
     }
     hipStreamSynchronize(st);
@@ -367,10 +425,10 @@ static int profile_impl(const S2kOp* ops, int begin, int end, void* const* bases
         for (int k = 0; k <= S2K_N_KINDS; ++k) { ms_by_kind[k] = 0.0f; launches_by_kind[k] = 0; }
         for (int i = 0; i < done; ++i) {
             float ms = 0.0f;
-            hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+            if (!fused[i]) hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
             const int k = ops[begin + i].kind;
             if (ms_per_op) ms_per_op[i] = ms;
-            if (k > 0 && k <= S2K_N_KINDS) { ms_by_kind[k] += ms; launches_by_kind[k] += 1; }
+            if (k > 0 && k <= S2K_N_KINDS && !fused[i]) { ms_by_kind[k] += ms; launches_by_kind[k] += 1; }
         }
     }
     for (int i = 0; i <= n; ++i) hipEventDestroy(ev[i]);

@@ -51,6 +51,12 @@ FLAG_SPLIT = 64     # CONV / WGRAD, f32-SPLIT plans only: the stage computes its
                     # Only the shapes of plan/split.py carry it; a flagged stage runs on the split kernels or fails (S2K_EINVAL).
 FLAG_DMA = 8        # CONV: take the LDS-DMA ring kernel (csrc/conv_dma.hip) for every shape it supports, not only where its launcher's
                     # measured routing rule sends a stage (tests cover all of its tiles this way; plans leave the choice to the launcher)
+FLAG_CHAIN = 128    # first BN_BWD_APPLY of a small-plane depthwise backward chain (unet_plan.mark_dw_chain): this record and the next three
+                    # - DWCONV_WGRAD, DWCONV_DGRAD, the expand BatchNorm's BN_BWD_APPLY - MAY run as one kernel (csrc/dwconv.hip,
+                    # dw_bwd_chain_kernel), and what is written only for use inside the chain is dead outside it: the DWCONV_DGRAD
+                    # output before the second APPLY and its STATS2 (the fused kernel never writes STATS2; every other tensor ends
+                    # up as the four stages leave it).  The records themselves are unchanged: the emulator and an executor that
+                    # declines the flag run the four stages one by one.
 
 # BN_FINALIZE folded into the first consumer of its {scale, shift} (a 5 us launch per BatchNorm otherwise: 126 per U-Net step):
 # the consumer's BNV becomes an OUTPUT computed from FSTATS (NREP replicas of {sum, sumsq}[C], FCOUNT elements per channel) with

@@ -890,6 +890,7 @@ def finish_plan(p: "_P", layout: ParamLayout, training: bool, bucket_floats: int
         mark_bf16(p, bwd)
     if getattr(p, "split", False):
         mark_split(p, bwd)
+    mark_dw_chain(p, bwd, segments)
     return segments, bwd
 
 
@@ -1021,6 +1022,67 @@ def mark_split(p: "_P", bwd) -> None:
     for f in packs:
         f["SPLIT_BASE"] = base
     p.wpack.top = base + 3 * ((base + 1) // 2) + 256
+
+
+def mark_dw_chain(p: "_P", bwd, segments=None) -> int:
+    """The small-plane depthwise backward chain (opdefs.FLAG_CHAIN): for every MBConv block the backward runs BN_BWD_APPLY (the
+    depthwise BatchNorm, g' recomputed) -> DWCONV_WGRAD -> DWCONV_DGRAD (+ the expand BatchNorm's sums) -> BN_BWD_APPLY (the expand
+    BatchNorm) over one expanded tensor: 11 HBM passes and 4 launches whose intermediate tensors nobody else reads.  On 8 x 8 and
+    16 x 16 planes at stride 1 a workgroup that owns a channel owns the whole chain (csrc/dwconv.hip, dw_bwd_chain_kernel).  The
+    records stay as they are - the emulator runs them one by one - and the first one carries the flag where ALL of this holds: the
+    four kinds are consecutive inside one backward segment, the tensor references chain up, train-mode f32 in place (bf16-mixed
+    plans write the second dY as bf16: left alone), and no later record reads what the fused kernel never writes (the data
+    gradient's STATS2).  Returns the number of chains marked."""
+    if bwd is None or tune("S2K_DW_CHAIN", "1") != "1":
+        return 0
+    ops = bwd.ops
+    seg_end = {}
+    for (a, b, _lo, _hi) in (segments or [(0, len(ops), 0, 0)]):
+        for i in range(a, b):
+            seg_end[i] = b
+    bad_flags = D.FLAG_BF16 | D.FLAG_SPLIT
+    kinds = ("BN_BWD_APPLY", "DWCONV_WGRAD", "DWCONV_DGRAD", "BN_BWD_APPLY")
+
+    def same(a, b):
+        return isinstance(a, TRef) and isinstance(b, TRef) and a.ref == b.ref
+
+    marked = 0
+    for i in range(len(ops) - 3):
+        if tuple(k for k, _ in ops[i:i + 4]) != kinds or seg_end.get(i, 0) < i + 4:
+            continue
+        a1, wg, dg, a2 = (f for _, f in ops[i:i + 4])
+        if any(f.get("_flags", 0) & bad_flags for f in (a1, wg, dg, a2)):
+            continue
+        dy, x, g, st2 = a1.get("DY"), dg.get("XRAW"), dg.get("G"), dg.get("STATS2")
+        if not (same(a1.get("GP"), dy) and same(wg.get("DY"), dy) and same(dg.get("DY"), dy)
+                and same(wg.get("X"), x) and same(a2.get("Y"), x) and same(a2.get("GP"), g) and same(a2.get("DY"), g)
+                and same(a2.get("STATS2"), st2) and same(wg.get("BNV"), dg.get("BNV")) and same(a2.get("BNV"), dg.get("BNV"))):
+            continue
+        if not (a1.get("ACT") == D.ACT_SILU and isinstance(a1.get("PS"), TRef) and isinstance(a1.get("MULBC"), TRef)
+                and isinstance(a1.get("ADDBC"), TRef) and a1.get("COEF") is None and not a1.get("EVAL") and not a1.get("OUT_BF16")):
+            continue
+        if not (a2.get("COEF") is None and not a2.get("ACT") and a2.get("PS") is None and a2.get("MULBC") is None
+                and a2.get("ADDBC") is None and not a2.get("EVAL") and not a2.get("OUT_BF16")):
+            continue
+        geo = ("B", "C", "H", "W", "K", "STRIDE", "PAD_T", "PAD_L", "HO", "WO", "PRO")
+        K, W = dg["K"], dg["W"]
+        if not (all(wg[k] == dg[k] for k in geo) and dg["STRIDE"] == 1 and dg["PRO"] == D.PRO_SILU and not dg.get("BETA")
+                and dg["H"] == W and W in (8, 16) and K in (3, 5) and dg["HO"] == W and dg["WO"] == W
+                and dg["PAD_T"] == (K - 1) // 2 and dg["PAD_L"] == (K - 1) // 2):
+            continue
+        if not all(f["B"] == dg["B"] and f["C"] == dg["C"] and f["HW"] == W * W for f in (a1, a2)):
+            continue
+        dead = [(t.base, t.off, t.off + t.nbytes) for t in (st2,)]
+        live = False
+        for _k2, f2 in ops[i + 4:]:
+            for v in f2.values():
+                if isinstance(v, TRef) and any(v.base == b and v.off < hi and lo < v.off + v.nbytes for (b, lo, hi) in dead):
+                    live = True
+        if live:
+            continue
+        a1["_flags"] = a1.get("_flags", 0) | D.FLAG_CHAIN
+        marked += 1
+    return marked
 
 
 def fold_bn_finalize(prog: Program) -> int:
