@@ -92,6 +92,13 @@ int s2k_program_profile_ops(const S2kOp* ops, int begin, int end, void* const* b
  * 10 on all four records of a small-plane depthwise backward chain (BN_BWD_APPLY flagged S2K_FLAG_CHAIN, DWCONV_WGRAD,
  * DWCONV_DGRAD, BN_BWD_APPLY) that ran as ONE kernel (dw_bwd_chain_kernel): its time is reported on the first record, the other
  * three report 0 ms and no launch.
+ * BatchNorm / squeeze-excitation / residual / reduction stages (csrc/ew.hip): 0 for their generic kernels (plane_reduce_kernel,
+ * plane_map_kernel, se_bn_sums_kernel, bn_bwd_reduce_kernel, se_fc_bwd_a1 / _a2 / _b_kernel, ...); 11 for the wave-per-channel
+ * small-plane kernels (SE_POOL se_pool_small_kernel, SE_BN_SUMS se_bn_sums_small_kernel, BN_BWD_APPLY bn_bwd_apply_small_kernel,
+ * BN_RESIDUAL bn_residual_small_kernel); 12 for the workgroup-per-plane kernels (SE_POOL se_pool_big_kernel, SE_BN_SUMS
+ * se_bn_sums_big_kernel); 13 for CHANNEL_SUM's channel_sum_rows_kernel; 14 for SE_FC_BWD's se_fc_bwd_small_kernel - SE_FC_BWD
+ * reports the route of its data-gradient phase, whichever kernel formed its parameter gradients; 15 for SE_FC_WGRAD's
+ * se_fc_wgrad_tile_kernel.
  * bench.py uses it to attribute time and algorithmic FLOPs to the kernel names a rocprofv3 trace shows. */
 int s2k_program_profile_variants(const S2kOp* ops, int begin, int end, void* const* bases, int n_bases, void* stream,
                                  float* ms_per_op, int* variant_per_op);

@@ -130,7 +130,10 @@ def profile_variants(packed: np.ndarray, bases: Bases, stream: int):
     """(ms per stage, variant per stage): the kernel family each stage's launcher picked (include/s2k.h,
     s2k_program_profile_variants): 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads, 5 f32-split;
     depthwise stages: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop; ViT stages: 8 the
-    LayerNorm row kernel (0 its tile kernel), 9 the scalar MAE-loss kernel (0 its float4 form)."""
+    LayerNorm row kernel (0 its tile kernel), 9 the scalar MAE-loss kernel (0 its float4 form); 10 a depthwise backward chain run as
+    one kernel; the BatchNorm / SE / residual / reduction stages of csrc/ew.hip: 0 their generic kernels, 11 the wave-per-channel
+    small-plane kernels, 12 the workgroup-per-plane kernels, 13 channel_sum_rows_kernel, 14 se_fc_bwd_small_kernel (SE_FC_BWD
+    reports its data-gradient route), 15 se_fc_wgrad_tile_kernel."""
     ms = np.zeros(len(packed), dtype=np.float32)
     var = np.zeros(len(packed), dtype=np.int32)
     with _guard(bases):

@@ -318,7 +318,12 @@ inline int tune_int(const char* name, int dflt) {
 // 1 = the producer/consumer kernel (conv_pc_kernel / wgrad_pc_kernel), 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads, 5 f32-split;
 // depthwise stages: 0 = the band kernels, 6 = the wave-per-channel plane kernels (dwconv_*_plane_kernel, dwconv_*_plane_s2_kernel),
 // 7 = dwconv_wgrad_kernel's image loop (bloop > 0); ViT stages: 8 = chan_ln_fwd_rows_kernel (0 = the tile kernel), 9 = the scalar
-// form of mae_loss_rows_kernel (0 = its float4 form); 10 = all four records of a depthwise backward chain run as one dw_bwd_chain_kernel.
+// form of mae_loss_rows_kernel (0 = its float4 form); 10 = all four records of a depthwise backward chain run as one dw_bwd_chain_kernel;
+// the BatchNorm / SE / residual / reduction stages of ew.hip: 0 = their generic kernels (plane_reduce_kernel, plane_map_kernel,
+// se_bn_sums_kernel, bn_bwd_reduce_kernel, the a1 / a2 / b SE kernels), 11 = the wave-per-channel small-plane kernels
+// (se_pool_small_kernel, se_bn_sums_small_kernel, bn_bwd_apply_small_kernel, bn_residual_small_kernel), 12 = the workgroup-per-plane
+// kernels (se_pool_big_kernel, se_bn_sums_big_kernel), 13 = channel_sum_rows_kernel, 14 = se_fc_bwd_small_kernel (SE_FC_BWD reports the
+// route of its data-gradient phase), 15 = se_fc_wgrad_tile_kernel (SE_FC_WGRAD).
 // The full list is in include/s2k.h.
 extern thread_local int g_s2k_variant;
 

@@ -470,6 +470,7 @@ int launch_se_pool(const S2kOp& op, const Ctx& c) {
         const int B = op.d[S2K_SE_POOL_D_B], C = op.d[S2K_SE_POOL_D_C], HW = op.d[S2K_SE_POOL_D_HW];
         if (HW >= 4096 && (HW & 3) == 0 && (int64_t)B * C <= 8192) {
             hipLaunchKernelGGL(se_pool_big_kernel, dim3((unsigned)(B * C)), dim3(NTHREADS), 0, c.stream, y, bnv, pool, C, HW, pro, fold);
+            g_s2k_variant = 12;
             return S2K_OK;
         }
         if (HW <= 256 && (HW & 3) == 0 && B > 1) {
@@ -477,6 +478,7 @@ int launch_se_pool(const S2kOp& op, const Ctx& c) {
             while (4 * lpp < HW) lpp <<= 1;
             const int bsplit = std::max(1, std::min(cdiv(B, 64 / lpp), cdiv(2048, C)));     // >= ~2048 waves in all
             hipLaunchKernelGGL(se_pool_small_kernel, dim3(cdiv(C, 4), bsplit), dim3(NTHREADS), 0, c.stream, y, bnv, pool, B, C, HW, pro, lpp, fold);
+            g_s2k_variant = 11;
             return S2K_OK;
         }
     }
@@ -656,6 +658,7 @@ int launch_se_bn_sums(const S2kOp& op, const Ctx& c) {
     const int64_t nplanes = (int64_t)B * C;
     if (HW >= 4096 && (HW & 3) == 0 && nplanes <= 8192) {
         hipLaunchKernelGGL(se_bn_sums_big_kernel, dim3((unsigned)nplanes), dim3(NTHREADS), 0, c.stream, g, y, bnv, dgate, ps, C, HW, nplanes);
+        g_s2k_variant = 12;
         return S2K_OK;
     }
     if (HW <= 64 && (HW & 3) == 0 && B > 1) {
@@ -663,6 +666,7 @@ int launch_se_bn_sums(const S2kOp& op, const Ctx& c) {
         while (4 * lpp < HW) lpp <<= 1;
         const int bsplit = std::max(1, std::min(cdiv(B, 64 / lpp), cdiv(2048, C)));
         hipLaunchKernelGGL(se_bn_sums_small_kernel, dim3(cdiv(C, 4), bsplit), dim3(NTHREADS), 0, c.stream, g, y, bnv, dgate, ps, B, C, HW, lpp);
+        g_s2k_variant = 11;
         return S2K_OK;
     }
     const unsigned blocks = (unsigned)cdiv64(nplanes, 4);
@@ -743,6 +747,7 @@ int launch_channel_sum(const S2kOp& op, const Ctx& c) {
     const int B = op.d[S2K_CHANNEL_SUM_D_B], C = op.d[S2K_CHANNEL_SUM_D_C], HW = op.d[S2K_CHANNEL_SUM_D_HW];
     if (B > 0 && C >= 256 && HW > 0 && HW <= 512) {
         hipLaunchKernelGGL(channel_sum_rows_kernel, dim3(C), dim3(NTHREADS), 0, c.stream, g, out, B, C, HW);
+        g_s2k_variant = 13;
         return S2K_OK;
     }
     return launch_plane_reduce<2>(g, nullptr, nullptr, out, op.d[S2K_CHANNEL_SUM_D_B], op.d[S2K_CHANNEL_SUM_D_C],
@@ -996,6 +1001,7 @@ static void launch_se_fc_param_grads(const float* dgp, const float* hs, const fl
     if (Q <= SEW_QMAX) {
         const size_t lds = (size_t)(2 * SEW_BT * Q + 2 * SEW_BT * SEW_CT) * sizeof(float);       // <= 59,392 bytes
         hipLaunchKernelGGL(se_fc_wgrad_tile_kernel, dim3(cdiv(C, SEW_CT)), dim3(NTHREADS), lds, st, dgp, hs, dhp, pool, dw1, db1, dw2, db2, B, C, Q);
+        g_s2k_variant = 15;
         return;
     }
     const int blocks = (int)std::min<int64_t>(cdiv64((int64_t)C * Q, 256), 1024);
@@ -1102,15 +1108,18 @@ int launch_se_fc_bwd(const S2kOp& op, const Ctx& c) {
     }
     if (Q > 8192 || B > 65535) { set_error("se_fc_bwd: C/Q too large"); return S2K_EINVAL; }
     if ((size_t)(C + 1024) * 4 > 64000) { set_error("se_fc_bwd: C too large"); return S2K_EINVAL; }
-    if (Q <= 64) {
+    const bool small = Q <= 64;
+    if (small) {
         hipLaunchKernelGGL(se_fc_bwd_small_kernel, dim3(B), dim3(1024), (size_t)(C + 1024 + 64) * sizeof(float), c.stream, dgate, gate, hpre, w1, w2,
                            hs, dpool, C, Q);
+        g_s2k_variant = 14;
     } else {
     hipLaunchKernelGGL(se_fc_bwd_a1_kernel, dim3(cdiv(Q, 64), B), dim3(1024), (C + 1024) * sizeof(float), c.stream, dgate, gate, hpre, w2, hs, B, C, Q);
     hipLaunchKernelGGL(se_fc_bwd_a2_kernel, dim3(cdiv(C, NTHREADS), B), dim3(NTHREADS), Q * sizeof(float), c.stream, dgate, gate, hpre, w1, dpool, B, C, Q);
     }
     if (!params) return S2K_OK;
     launch_se_fc_param_grads(dgate, hs, hpre, pool, dw1, db1, dw2, db2, B, C, Q, c.stream);
+    g_s2k_variant = small ? 14 : 0;      // SE_FC_BWD reports its data-gradient route; SE_FC_WGRAD shows the parameter-gradient one
     return S2K_OK;
 }
 
@@ -1403,6 +1412,7 @@ static bool launch_bn_bwd_apply_small(const float* a, const float* y, const floa
     while (4 * lpp < HW) lpp <<= 1;
     const int bsplit = std::max(1, std::min(cdiv(B, 64 / lpp), cdiv(2048, C)));
     hipLaunchKernelGGL((bn_bwd_apply_small_kernel<MODE, OUT16>), dim3(cdiv(C, 4), bsplit), dim3(NTHREADS), 0, st, a, y, bnv, out, B, C, HW, lpp, fz);
+    g_s2k_variant = 11;
     return true;
 }
 
@@ -1519,6 +1529,7 @@ int launch_bn_residual(const S2kOp& op, const Ctx& c) {
             const int bsplit = std::max(1, std::min(cdiv(B, 64 / lpp), cdiv(2048, C)));
             hipLaunchKernelGGL(bn_residual_small_kernel, dim3(cdiv(C, 4), bsplit), dim3(NTHREADS), 0, c.stream, ident, y, bnv, noise, xout, B, C, HW,
                                op.f[S2K_BN_RESIDUAL_F_KEEP], lpp, fold);
+            g_s2k_variant = 11;
             return S2K_OK;
         }
     }

@@ -2,7 +2,11 @@
 (`s2k_program_run` on a one-record program) and compared with the oracle's CPU statement of the
 same stage (oracle/ops_ref.py) on identical seeded bytes.  fp32 tolerance is stated per case
 (float atomics make sums order-dependent; 1e-4 relative to the tensor's max is the bar here, the
-network-level bar of BASELINE.json is 1e-3)."""
+network-level bar of BASELINE.json is 1e-3).
+Case.run can hold a stage to the kernel family its launcher must take (want_variant), to a float64 run of the oracle (ref64), to
+its bar per column / per channel (per_column, per_channel) and to leaving the rest of the arena untouched (untouched).  The
+BatchNorm / SE / residual / reduction cases below are pinned to the family tests/ew_dispatch.py restates; their routing boundaries,
+loop edges and forms are covered row by row in tests/test_ew_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -11,6 +15,7 @@ import s2lc_amd  # noqa: F401
 from oracle import ops_ref
 from s2lc_amd.plan import opdefs as D
 from s2lc_amd.plan.program import Arena, Program
+from tests import ew_dispatch as EW
 
 pytestmark = pytest.mark.gpu
 
@@ -111,14 +116,25 @@ class Case:
         wdt = {"f32": torch.float64, "bf16": torch.float32}.get(ref.dtype, _DT[ref.dtype])
         return image[2 * ref.off:2 * ref.off + ref.numel * wdt.itemsize].view(wdt).reshape(ref.shape)
 
-    def run(self, kind, outputs, tol=1e-4, sum0=(), pre=(), want_variant=None, per_column=(), ref64=False, **fields):
+    def run(self, kind, outputs, tol=1e-4, sum0=(), pre=(), want_variant=None, per_column=(), ref64=False, per_channel=(), untouched=False,
+            **fields):
         """sum0: outputs compared after summing their leading (statistics-replica) dimension.
         pre: stage records to run first (e.g. WEIGHT_PACK).  want_variant: the kernel family the stage must have taken
         (s2k_program_profile_variants, include/s2k.h: 0 generic, 1 producer / consumer, 2 bf16 MFMA, 3 LDS-DMA ring, 4 quad reads,
         5 f32-split; depthwise: 0 band kernels, 6 wave-per-channel plane kernels, 7 the weight gradient's image loop; ViT stages:
-        CHAN_LN_FWD 0 tile kernel, 8 row kernel; MAE_LOSS_FWD / _BWD 0 float4 kernel, 9 scalar kernel).
+        CHAN_LN_FWD 0 tile kernel, 8 row kernel; MAE_LOSS_FWD / _BWD 0 float4 kernel, 9 scalar kernel; 10 a depthwise backward chain
+        run as one kernel; the stages of csrc/ew.hip: 0 their generic kernels, 11 the wave-per-channel small-plane kernels, 12 the
+        workgroup-per-plane kernels, 13 channel_sum_rows_kernel, 14 se_fc_bwd_small_kernel - SE_FC_BWD reports its data-gradient
+        route -, 15 se_fc_wgrad_tile_kernel).
         per_column: outputs whose every last-dim column must also meet `tol` against that column's own max |ref| (a wrong
-        column among larger ones - e.g. a ragged last channel tile - hides under the whole tensor's max).
+        column among larger ones - e.g. a ragged last channel tile - hides under the whole tensor's max); with ref64 also
+        against the float64 run.
+        per_channel: the same for (B, C, HW) outputs: every channel c against its own max |ref| over (b, hw), f32 oracle and
+        (ref64) float64.
+        untouched: every byte of the arena outside the tensors the records write (opdefs.WRITES; BNV / FRM / FRV of a foldable
+        stage only when FSTATS is given) must be what was uploaded - the other tensors, NaN-filled ones included, bit for bit, and
+        the slack between and behind the allocations still zero.
+        The worst per-column / per-channel figures of the last call are left in self.parts: {output: (f32 oracle, float64 or None)}.
         ref64: the outputs must also meet `tol` against a float64 run of the oracle (every f32 tensor held as float64 at twice its
         offset, as plan_harness.make_bases(wide=True) lays out a plan), so that an error the f32 oracle shares cannot hide.
         Returns {output: (error against the f32 oracle, error against float64 or None)}."""
@@ -127,7 +143,26 @@ class Case:
             prog.add(k, **f)
         prog.add(kind, **fields)
         got, cpu, wide = self.execute(prog.pack(), ref64=ref64, want_variant=want_variant, kind=kind)
+        self.got = got          # the GPU's byte image of the arena, for checks beyond the tolerances
+        if untouched:
+            sent = torch.zeros_like(got)
+            for name, (ref, data) in self.items.items():
+                sent[ref.off:ref.off + ref.nbytes] = data.contiguous().reshape(-1).view(torch.uint8)
+            free = torch.ones(got.numel(), dtype=torch.bool)
+            for k, f in prog.ops:
+                folded = f.get("FSTATS") is not None
+                for w in D.WRITES[k]:
+                    r = f.get(w)
+                    if r is None or (k in D.FOLD_KINDS and w in ("BNV", "FRM", "FRV") and not folded):
+                        continue
+                    free[r.off:r.off + r.nbytes] = False
+            bad = torch.nonzero((got != sent) & free).reshape(-1)
+            if bad.numel():
+                at = int(bad[0])
+                owner = [n for n, (r, _) in self.items.items() if r.off <= at < r.off + r.nbytes] or ["the slack between allocations"]
+                raise AssertionError(f"{kind}: {bad.numel()} bytes outside the stage's outputs changed, first at byte {at} ({owner[0]})")
         errs = {}
+        self.parts = {}
         for name in outputs:
             ref, _ = self.items[name]
             a = self.read(got, name).reshape(-1).double()
@@ -149,12 +184,25 @@ class Case:
                 err64 = (a.reshape(t.shape) - t).abs().max().item() / d64
                 assert err64 < tol, f"{kind}:{name}: rel err {err64:.3e} against float64 (max |ref| {d64:.3e})"
             errs[name] = (err, err64)
-            if name in per_column:
-                n = ref.shape[-1]
-                a, b = a.reshape(-1, n), b.reshape(-1, n)
-                cerr = (a - b).abs().amax(0) / b.abs().amax(0).clamp_min(1e-20)
-                col = int(cerr.argmax())
-                assert cerr[col] < tol, f"{kind}:{name}: column {col} of {n}: rel err {cerr[col]:.3e} (its max |ref| {b[:, col].abs().max():.3e})"
+            if name in per_column or name in per_channel:
+                if name in per_column:
+                    n, what = ref.shape[-1], "column"
+                    part = lambda v: v.reshape(-1, n)                                                 # noqa: E731
+                else:
+                    n, what = ref.shape[1], "channel"
+                    part = lambda v: v.reshape(ref.shape[0], n, -1).transpose(0, 1).reshape(n, -1).t()   # noqa: E731
+                worst = []
+                for r_, against in ((b, ""), (t if wide is not None else None, " against float64")):
+                    if r_ is None:
+                        worst.append(None)
+                        continue
+                    pa, pr = part(a), part(r_)
+                    cerr = (pa - pr).abs().amax(0) / pr.abs().amax(0).clamp_min(1e-20)
+                    col = int(cerr.argmax())
+                    worst.append(float(cerr[col]))
+                    assert cerr[col] < tol, (f"{kind}:{name}: {what} {col} of {n}: rel err {cerr[col]:.3e}{against} "
+                                             f"(its max |ref| {pr[:, col].abs().max():.3e})")
+                self.parts[name] = tuple(worst)
         return errs
 
 
@@ -276,7 +324,7 @@ def test_dy_stored_as_bf16_between_bn_apply_and_its_1x1_readers(B, M, C, H, W):
     dg, db = c.t("dgamma", (M,)), c.t("dbeta", (M,))
     dy = c.t("dy", (B, M, HW), "nan", "bf16")
     c.run("BN_BWD_APPLY", ["dy", "dgamma", "dbeta"], 8e-3, GP=gp, Y=y, BNV=bnv, COEF=None, DY=dy, STATS2=st2, GAMMA=gam, DGAMMA=dg, DBETA=db,
-          COUNT=B * HW, B=B, C=M, HW=HW, NREP=nrep, OUT_BF16=1)
+          COUNT=B * HW, B=B, C=M, HW=HW, NREP=nrep, OUT_BF16=1, want_variant=EW.dispatch("BN_BWD_APPLY", B=B, C=M, HW=HW, NREP=nrep, OUT_BF16=1).family)
     # 2. the data gradient reads it: dX[c] = sum_m W[m][c] * dY[m]   (identical operand values on both sides: 1e-4)
     c2 = Case(45)
     dyb = c2.t("dy", (B, M, H, W), "randn", "bf16", scale=0.3)
@@ -878,7 +926,8 @@ def test_bn_backward_trio(B, C, HW, variant):
     noise = c.t("noise", (B,), "rand") if variant == "none_dc" else None
     act = {"relu": 3, "silu_se": 2, "none_dc": 0}[variant]
     c.run("BN_BWD_REDUCE", ["gout", "stats2"], 1e-4, sum0=("stats2",), G=g, Y=y, BNV=bnv, MULBC=mul, ADDBC=add, NOISE=noise,
-          GOUT=gout, STATS2=st2, B=B, C=C, HW=HW, ACT=act, NREP=nrep, KEEP=0.6, ADDSCALE=1.0 / HW)
+          GOUT=gout, STATS2=st2, B=B, C=C, HW=HW, ACT=act, NREP=nrep, KEEP=0.6, ADDSCALE=1.0 / HW,
+          want_variant=EW.dispatch("BN_BWD_REDUCE", B=B, C=C, HW=HW).family)
     c2 = Case(7)
     st2 = c2.t("stats2", (2, 2, C), torch.randn(2, 2, C, dtype=torch.float64) * 10, "f64")
     gam = c2.t("gamma", (C,), "pos")
@@ -886,12 +935,13 @@ def test_bn_backward_trio(B, C, HW, variant):
     dg, db = c2.t("dgamma", (C,)), c2.t("dbeta", (C,))
     coef = c2.t("coef", (3, C), "nan")
     c2.run("BN_BWD_FINALIZE", ["dgamma", "dbeta", "coef"], 1e-5, STATS2=st2, GAMMA=gam, BNV=bnv, DGAMMA=dg, DBETA=db,
-           COEF=coef, COUNT=B * HW, C=C, NREP=2)
+           COEF=coef, COUNT=B * HW, C=C, NREP=2, want_variant=EW.dispatch("BN_BWD_FINALIZE", C=C, NREP=2).family)
     c3 = Case(8)
     gp, y = c3.t("gp", (B, C, HW)), c3.t("y", (B, C, HW))
     bnv, coef = c3.bnv("bnv", C), c3.t("coef", (3, C))
     dy = c3.t("dy", (B, C, HW), "nan")
-    c3.run("BN_BWD_APPLY", ["dy"], 1e-5, GP=gp, Y=y, BNV=bnv, COEF=coef, DY=dy, B=B, C=C, HW=HW)
+    c3.run("BN_BWD_APPLY", ["dy"], 1e-5, GP=gp, Y=y, BNV=bnv, COEF=coef, DY=dy, B=B, C=C, HW=HW,
+           want_variant=EW.dispatch("BN_BWD_APPLY", B=B, C=C, HW=HW, COEF=True).family)
     # the form the planner emits: no COEF table, FINALIZE's arithmetic inside APPLY (replica sums, dgamma / dbeta)
     for nrep in (2, 20):
         c4 = Case(9)
@@ -901,7 +951,7 @@ def test_bn_backward_trio(B, C, HW, variant):
         dg, db = c4.t("dgamma", (C,)), c4.t("dbeta", (C,))
         dy = c4.t("dy", (B, C, HW), "nan")
         c4.run("BN_BWD_APPLY", ["dy", "dgamma", "dbeta"], 1e-5, GP=gp, Y=y, BNV=bnv, COEF=None, DY=dy, STATS2=st2, GAMMA=gam, DGAMMA=dg,
-               DBETA=db, COUNT=B * HW, B=B, C=C, HW=HW, NREP=nrep)
+               DBETA=db, COUNT=B * HW, B=B, C=C, HW=HW, NREP=nrep, want_variant=EW.dispatch("BN_BWD_APPLY", B=B, C=C, HW=HW, NREP=nrep).family)
 
 
 @pytest.mark.parametrize("B,C,HW,ident,noise", [(2, 24, 256, True, True), (3, 10, 49, False, False), (1, 3, 9000, True, False),
@@ -912,7 +962,8 @@ def test_bn_residual(B, C, HW, ident, noise):
     idt = c.t("ident", (B, C, HW)) if ident else None
     nz = c.t("noise", (B,), "rand") if noise else None
     out = c.t("xout", (B, C, HW), "nan")
-    c.run("BN_RESIDUAL", ["xout"], 1e-6, Y=y, BNV=bnv, IDENT=idt, NOISE=nz, XOUT=out, B=B, C=C, HW=HW, KEEP=0.55)
+    c.run("BN_RESIDUAL", ["xout"], 1e-6, Y=y, BNV=bnv, IDENT=idt, NOISE=nz, XOUT=out, B=B, C=C, HW=HW, KEEP=0.55,
+          want_variant=EW.dispatch("BN_RESIDUAL", B=B, C=C, HW=HW).family)
 
 
 @pytest.mark.parametrize("B,C,HW", [(2, 48, 256), (3, 20, 49), (1, 5, 9000), (11, 130, 64), (3, 7, 36), (3, 5, 4100 * 4)])   # (last: workgroup per plane)
@@ -920,15 +971,16 @@ def test_se_pool_bwd_reduce_channel_sum(B, C, HW):
     c = Case(10)
     y, bnv = c.t("y", (B, C, HW)), c.bnv("bnv", C)
     pool = c.t("pool", (B, C), "nan")
-    c.run("SE_POOL", ["pool"], 1e-5, Y=y, BNV=bnv, POOL=pool, B=B, C=C, HW=HW, PRO=2)
+    c.run("SE_POOL", ["pool"], 1e-5, Y=y, BNV=bnv, POOL=pool, B=B, C=C, HW=HW, PRO=2, want_variant=EW.dispatch("SE_POOL", B=B, C=C, HW=HW).family)
     c = Case(11)
     g, y, bnv = c.t("g", (B, C, HW)), c.t("y", (B, C, HW)), c.bnv("bnv", C)
     dg = c.t("dgate", (B, C), "nan")
-    c.run("SE_BWD_REDUCE", ["dgate"], 1e-4, G=g, Y=y, BNV=bnv, DGATE=dg, B=B, C=C, HW=HW, PRO=2)
+    c.run("SE_BWD_REDUCE", ["dgate"], 1e-4, G=g, Y=y, BNV=bnv, DGATE=dg, B=B, C=C, HW=HW, PRO=2,
+          want_variant=EW.dispatch("SE_BWD_REDUCE", B=B, C=C, HW=HW).family)
     c = Case(12)
     g = c.t("g", (B, C, HW))
     out = c.t("out", (C,), "randn")
-    c.run("CHANNEL_SUM", ["out"], 1e-4, G=g, OUT=out, B=B, C=C, HW=HW)
+    c.run("CHANNEL_SUM", ["out"], 1e-4, G=g, OUT=out, B=B, C=C, HW=HW, want_variant=EW.dispatch("CHANNEL_SUM", B=B, C=C, HW=HW).family)
 
 
 @pytest.mark.parametrize("B,C,Q", [(2, 48, 4), (3, 144, 6), (2, 3072, 128), (1, 1056, 44), (5, 768, 32), (2, 1824, 76), (3, 1100, 64),
@@ -939,7 +991,8 @@ def test_se_fc_and_backward(B, C, Q):
     w1, b1 = c.t("w1", (Q, C), scale=C ** -0.5), c.t("b1", (Q,))
     w2, b2 = c.t("w2", (C, Q), scale=Q ** -0.5), c.t("b2", (C,))
     hpre, gate = c.t("hpre", (B, Q), "nan"), c.t("gate", (B, C), "nan")
-    c.run("SE_FC", ["hpre", "gate"], 1e-5, POOL=pool, W1=w1, B1=b1, W2=w2, B2=b2, HPRE=hpre, GATE=gate, B=B, C=C, CSQ=Q)
+    c.run("SE_FC", ["hpre", "gate"], 1e-5, POOL=pool, W1=w1, B1=b1, W2=w2, B2=b2, HPRE=hpre, GATE=gate, B=B, C=C, CSQ=Q,
+          want_variant=EW.dispatch("SE_FC", B=B, C=C, CSQ=Q).family)
     c = Case(14)
     dgate, gate = c.t("dgate", (B, C)), c.t("gate", (B, C), "rand")
     hpre, pool = c.t("hpre", (B, Q)), c.t("pool", (B, C), "rand")
@@ -947,7 +1000,8 @@ def test_se_fc_and_backward(B, C, Q):
     dw1, db1, dw2, db2 = c.t("dw1", (Q, C)), c.t("db1", (Q,)), c.t("dw2", (C, Q)), c.t("db2", (C,))
     dpool, hs = c.t("dpool", (B, C), "nan"), c.t("hs", (B, Q), "nan")
     c.run("SE_FC_BWD", ["dw1", "db1", "dw2", "db2", "dpool"], 1e-4, DGATE=dgate, GATE=gate, HPRE=hpre, POOL=pool, W1=w1,
-          W2=w2, DW1=dw1, DB1=db1, DW2=dw2, DB2=db2, DPOOL=dpool, HS=hs, B=B, C=C, CSQ=Q)
+          W2=w2, DW1=dw1, DB1=db1, DW2=dw2, DB2=db2, DPOOL=dpool, HS=hs, B=B, C=C, CSQ=Q,
+          want_variant=EW.dispatch("SE_FC_BWD", B=B, C=C, CSQ=Q, DW1=True).family)
     # split form (what the planner emits): data gradient first, parameter gradients as a stage of their own
     c = Case(14)
     dgate, gate = c.t("dgate", (B, C)), c.t("gate", (B, C), "rand")
@@ -958,7 +1012,8 @@ def test_se_fc_and_backward(B, C, Q):
     first = ("SE_FC_BWD", dict(DGATE=dgate, GATE=gate, HPRE=hpre, POOL=pool, W1=w1, W2=w2, DW1=None, DB1=None, DW2=None, DB2=None,
                                DPOOL=dpool, HS=hs, B=B, C=C, CSQ=Q))
     c.run("SE_FC_WGRAD", ["dw1", "db1", "dw2", "db2", "dpool", "hs", "dgate", "hpre"], 1e-4, pre=[first], DGP=dgate, HS=hs, DHP=hpre,
-          POOL=pool, DW1=dw1, DB1=db1, DW2=dw2, DB2=db2, B=B, C=C, CSQ=Q)
+          POOL=pool, DW1=dw1, DB1=db1, DW2=dw2, DB2=db2, B=B, C=C, CSQ=Q,
+          want_variant=[EW.dispatch("SE_FC_BWD", B=B, C=C, CSQ=Q).family, EW.dispatch("SE_FC_WGRAD", B=B, C=C, CSQ=Q).family])
 
 
 def test_axpy_memset():
@@ -1123,12 +1178,14 @@ def test_se_bn_two_pass_stages(B, C, HW):          # (<= 64 elements: channel-pe
     g, y = c.t("g", (B, C, HW)), c.t("y", (B, C, HW))
     bnv = c.bnv("bnv", C)
     dgate, ps = c.t("dgate", (B, C), "nan"), c.t("ps", (4, B, C), "nan")
-    c.run("SE_BN_SUMS", ["dgate", "ps"], 2e-4, G=g, Y=y, BNV=bnv, DGATE=dgate, PS=ps, B=B, C=C, HW=HW, ACT=D.ACT_SILU)
+    c.run("SE_BN_SUMS", ["dgate", "ps"], 2e-4, G=g, Y=y, BNV=bnv, DGATE=dgate, PS=ps, B=B, C=C, HW=HW, ACT=D.ACT_SILU,
+          want_variant=EW.dispatch("SE_BN_SUMS", B=B, C=C, HW=HW).family)
     c2 = Case(22)
     ps = c2.t("ps", (4, B, C), scale=5.0)
     mul, add = c2.t("mul", (B, C), "rand"), c2.t("add", (B, C))
     st2 = c2.t("st2", (2, C), "nan", "f64")
-    c2.run("SE_BN_COMBINE", ["st2"], 1e-6, PS=ps, MULBC=mul, ADDBC=add, STATS2=st2, B=B, C=C, ADDSCALE=1.0 / HW)
+    c2.run("SE_BN_COMBINE", ["st2"], 1e-6, PS=ps, MULBC=mul, ADDBC=add, STATS2=st2, B=B, C=C, ADDSCALE=1.0 / HW,
+           want_variant=EW.dispatch("SE_BN_COMBINE", B=B, C=C).family)
     c3 = Case(23)
     gp, y = c3.t("gp", (B, C, HW)), c3.t("y", (B, C, HW))
     bnv, gam = c3.bnv("bnv", C), c3.t("gamma", (C,), "pos")
@@ -1136,7 +1193,8 @@ def test_se_bn_two_pass_stages(B, C, HW):          # (<= 64 elements: channel-pe
     st2 = c3.t("st2", (1, 2, C), torch.randn(1, 2, C, dtype=torch.float64, generator=c3.gen) * 10, "f64")
     dg, db = c3.t("dgamma", (C,)), c3.t("dbeta", (C,))
     c3.run("BN_BWD_APPLY", ["gp", "dgamma", "dbeta"], 2e-5, GP=gp, Y=y, BNV=bnv, COEF=None, DY=gp, STATS2=st2, GAMMA=gam, DGAMMA=dg, DBETA=db,
-           MULBC=mul, ADDBC=add, COUNT=B * HW, B=B, C=C, HW=HW, NREP=1, ACT=D.ACT_SILU, ADDSCALE=1.0 / HW)
+           MULBC=mul, ADDBC=add, COUNT=B * HW, B=B, C=C, HW=HW, NREP=1, ACT=D.ACT_SILU, ADDSCALE=1.0 / HW,
+           want_variant=EW.dispatch("BN_BWD_APPLY", B=B, C=C, HW=HW, NREP=1, ACT=D.ACT_SILU, MULBC=True, ADDBC=True).family)
     # the same with SE_BN_COMBINE folded in: APPLY forms the sums from the plane sums itself
     c4 = Case(27)
     gp, y = c4.t("gp", (B, C, HW)), c4.t("y", (B, C, HW))
@@ -1145,7 +1203,8 @@ def test_se_bn_two_pass_stages(B, C, HW):          # (<= 64 elements: channel-pe
     ps = c4.t("ps", (4, B, C), scale=3.0)
     dg, db = c4.t("dgamma", (C,)), c4.t("dbeta", (C,))
     c4.run("BN_BWD_APPLY", ["gp", "dgamma", "dbeta"], 2e-5, GP=gp, Y=y, BNV=bnv, COEF=None, DY=gp, STATS2=None, GAMMA=gam, DGAMMA=dg, DBETA=db,
-           MULBC=mul, ADDBC=add, PS=ps, COUNT=B * HW, B=B, C=C, HW=HW, NREP=1, ACT=D.ACT_SILU, ADDSCALE=1.0 / HW)
+           MULBC=mul, ADDBC=add, PS=ps, COUNT=B * HW, B=B, C=C, HW=HW, NREP=1, ACT=D.ACT_SILU, ADDSCALE=1.0 / HW,
+           want_variant=EW.dispatch("BN_BWD_APPLY", B=B, C=C, HW=HW, NREP=1, ACT=D.ACT_SILU, MULBC=True, ADDBC=True, PS=True).family)
 
 
 @pytest.mark.parametrize("B,C,H,W,k,s", [(2, 13, 32, 32, 3, 2), (1, 3, 15, 22, 3, 2), (2, 4, 17, 17, 5, 2), (1, 2, 12, 20, 3, 3)])
@@ -1231,10 +1290,12 @@ def test_se_pool_and_bn_residual_with_folded_bn_finalize(B, C, HW):
     y = c.t("y", (B, C, HW))
     pool = c.t("pool", (B, C), "nan")
     fold, bnv = _fold_fields(c, C, B * HW, D.stats_replicas(C))
-    c.run("SE_POOL", ["pool", "bnv", "frm", "frv"], 1e-5, Y=y, BNV=bnv, POOL=pool, B=B, C=C, HW=HW, PRO=2, **fold)
+    c.run("SE_POOL", ["pool", "bnv", "frm", "frv"], 1e-5, Y=y, BNV=bnv, POOL=pool, B=B, C=C, HW=HW, PRO=2,
+          want_variant=EW.dispatch("SE_POOL", B=B, C=C, HW=HW, FSTATS=True, FNREP=D.stats_replicas(C)).family, **fold)
     c = Case(33)
     y = c.t("y", (B, C, HW))
     idt, nz = c.t("ident", (B, C, HW)), c.t("noise", (B,), "rand")
     out = c.t("xout", (B, C, HW), "nan")
     fold, bnv = _fold_fields(c, C, B * HW, D.stats_replicas(C))
-    c.run("BN_RESIDUAL", ["xout", "bnv", "frm", "frv"], 1e-5, Y=y, BNV=bnv, IDENT=idt, NOISE=nz, XOUT=out, B=B, C=C, HW=HW, KEEP=0.55, **fold)
+    c.run("BN_RESIDUAL", ["xout", "bnv", "frm", "frv"], 1e-5, Y=y, BNV=bnv, IDENT=idt, NOISE=nz, XOUT=out, B=B, C=C, HW=HW, KEEP=0.55,
+          want_variant=EW.dispatch("BN_RESIDUAL", B=B, C=C, HW=HW, FSTATS=True, FNREP=D.stats_replicas(C)).family, **fold)
