@@ -165,10 +165,6 @@ def op_conv(m: Mem, o):
         if bias is not None:
             y = y + bias.view(1, -1, 1, 1)
         dst = m.view(o["Y"], (B, M, Ho, Wo), strides=(YC * Ho * Wo, Ho * Wo, Wo, 1))
-    if o["STATS"] >= 0:
-        st = m.view(o["STATS"], (max(o["NREP"], 1), 2, M), "f64")[0]   # any replica: finalize sums them all
-        st[0] += y.double().sum((0, 2, 3))
-        st[1] += (y.double() ** 2).sum((0, 2, 3))
     if o.get("RES", -1) >= 0:
         res = m.view(o["RES"], tuple(dst.shape), strides=tuple(dst.stride()))
         # FLAG_RES_GELU_GRAD: the backward of "GELU, then this Linear's transpose" in one stage - times gelu'(RES) instead of + RES
@@ -177,6 +173,14 @@ def op_conv(m: Mem, o):
         dst.add_(y)
     else:
         dst.copy_(y)
+    if o["STATS"] >= 0:
+        # the statistics of the FINISHED rows - what Y holds now, residual and accumulate included - as every CONV kernel and the
+        # split-K tail take them (csrc/igemm.hip: "BatchNorm statistics of the finished rows"); no planned stage has STATS with
+        # RES or BETA, so only stage-level tests see the order
+        fin = dst.double()
+        st = m.view(o["STATS"], (max(o["NREP"], 1), 2, M), "f64")[0]   # any replica: finalize sums them all
+        st[0] += fin.sum((0, 2, 3))
+        st[1] += (fin ** 2).sum((0, 2, 3))
 
 
 def op_wgrad(m: Mem, o):

@@ -6,7 +6,9 @@ network-level bar of BASELINE.json is 1e-3).
 Case.run can hold a stage to the kernel family its launcher must take (want_variant), to a float64 run of the oracle (ref64), to
 its bar per column / per channel (per_column, per_channel) and to leaving the rest of the arena untouched (untouched).  The
 BatchNorm / SE / residual / reduction cases below are pinned to the family tests/ew_dispatch.py restates; their routing boundaries,
-loop edges and forms are covered row by row in tests/test_ew_kernels_gpu.py."""
+loop edges and forms are covered row by row in tests/test_ew_kernels_gpu.py.  The f32 CONV cases are pinned to the family
+tests/conv_dispatch.py restates (checked on the CPU by tests/test_conv_dispatch_cpu.py); the four dense-convolution kernels are covered
+instantiation by instantiation in tests/test_conv_kernels_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -28,6 +30,7 @@ class Case:
     def __init__(self, seed=0):
         self.arena = Arena(WS)
         self.items = {}
+        self.packed = []        # what this case's WEIGHT_PACK records write (pack): the f32 pack and its quad / bf16 copy
         self.gen = torch.Generator().manual_seed(seed)
 
     def t(self, name, shape, fill="randn", dtype="f32", scale=1.0):
@@ -69,12 +72,15 @@ class Case:
         if q4:      # the f32 quad copy of a 1x1 entry lives at DST bytes + Q4_BASE + 4 * dst_off
             dstq = self.t(f"packedq_{len(self.items)}", (KP * T, MP), "nan")
             fields["Q4_BASE"] = dstq.off - dst.off
+            self.packed += [dst, dstq]
             return ("WEIGHT_PACK", fields), dst, MP, dstq
         if not bf16:
+            self.packed.append(dst)
             return ("WEIGHT_PACK", fields), dst, MP
         # the bf16 copy of an entry lives at DST bytes + BF16_BASE + 2 * dst_off (plan: a mirror region behind the f32 packs)
         dst16 = self.t(f"packed16_{len(self.items)}", (KP * T * MP // 2,), "nan")
         fields["BF16_BASE"] = dst16.off - dst.off // 2
+        self.packed += [dst, dst16]
         return ("WEIGHT_PACK", fields), dst, MP, dst16
 
     def execute(self, packed, ref64=False, oracle=True, want_variant=None, kind=""):
@@ -82,9 +88,7 @@ class Case:
         in float64.  Returns the byte images (GPU result, f32 oracle or None, float64 oracle or None); read() takes a tensor out of one."""
         from s2lc_amd import _lib
 
-        cpu = torch.zeros(self.arena.top + 256, dtype=torch.uint8)
-        for name, (ref, data) in self.items.items():
-            cpu[ref.off:ref.off + ref.nbytes] = data.contiguous().reshape(-1).view(torch.uint8)
+        cpu = self.image()
         gpu = cpu.cuda()
         _lib.run(packed, _lib.Bases().set("WS", gpu), torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
@@ -97,8 +101,20 @@ class Case:
         got = gpu.cpu()
         if not oracle:
             return got, None, None
+        return (got,) + self.oracles(packed, ref64)
+
+    def image(self):
+        """the byte image of the arena as uploaded"""
+        cpu = torch.zeros(self.arena.top + 256, dtype=torch.uint8)
+        for name, (ref, data) in self.items.items():
+            cpu[ref.off:ref.off + ref.nbytes] = data.contiguous().reshape(-1).view(torch.uint8)
+        return cpu
+
+    def oracles(self, packed, ref64=False):
+        """packed records through ops_ref on this case's bytes, no GPU involved: (f32 image, float64 image or None)"""
+        cpu = self.image()
         wide = None
-        if ref64:       # (from the inputs as written: the f32 oracle below overwrites `cpu` in place)
+        if ref64:
             wide = torch.zeros(2 * cpu.numel(), dtype=torch.uint8)
             for name, (ref, data) in self.items.items():
                 wdt = {"f32": torch.float64, "bf16": torch.float32}.get(ref.dtype)
@@ -106,7 +122,7 @@ class Case:
                 wide[2 * ref.off:2 * ref.off + b.numel()] = b
             ops_ref.run_program(packed, {WS: wide}, D, wide=True)
         ops_ref.run_program(packed, {WS: cpu}, D)
-        return got, cpu, wide
+        return cpu, wide
 
     def read(self, image, name, wide=False):
         """tensor `name` out of a byte image of the arena (wide=True: the float64 layout, f32 held as f64 and bf16 as f32 at twice the offset)"""
@@ -133,7 +149,7 @@ class Case:
         (ref64) float64.
         untouched: every byte of the arena outside the tensors the records write (opdefs.WRITES; BNV / FRM / FRV of a foldable
         stage only when FSTATS is given) must be what was uploaded - the other tensors, NaN-filled ones included, bit for bit, and
-        the slack between and behind the allocations still zero.
+        the slack between and behind the allocations still zero.  (A WEIGHT_PACK record in `pre` writes the packs that pack() laid out.)
         The worst per-column / per-channel figures of the last call are left in self.parts: {output: (f32 oracle, float64 or None)}.
         ref64: the outputs must also meet `tol` against a float64 run of the oracle (every f32 tensor held as float64 at twice its
         offset, as plan_harness.make_bases(wide=True) lays out a plan), so that an error the f32 oracle shares cannot hide.
@@ -144,11 +160,14 @@ class Case:
         prog.add(kind, **fields)
         got, cpu, wide = self.execute(prog.pack(), ref64=ref64, want_variant=want_variant, kind=kind)
         self.got = got          # the GPU's byte image of the arena, for checks beyond the tolerances
+        self.ref = cpu          # ... and the f32 oracle's
         if untouched:
             sent = torch.zeros_like(got)
             for name, (ref, data) in self.items.items():
                 sent[ref.off:ref.off + ref.nbytes] = data.contiguous().reshape(-1).view(torch.uint8)
             free = torch.ones(got.numel(), dtype=torch.bool)
+            for r in (self.packed if any(k == "WEIGHT_PACK" for k, _ in prog.ops) else ()):
+                free[r.off:r.off + r.nbytes] = False
             for k, f in prog.ops:
                 folded = f.get("FSTATS") is not None
                 for w in D.WRITES[k]:
@@ -457,12 +476,12 @@ def test_conv1x1_producer_consumer(B, C1, H, W, M, pro, bias, stats, beta, want)
 
 
 @pytest.mark.parametrize("B,C1,H,W,M,bias,stats,beta,res,scratch", [
-    (32, 40, 16, 16, 240, False, True, 0, False, False),     # short reduction (K = 40 = two stages + a half stage), 256 x 128 tiles, statistics
-    (8, 24, 32, 32, 144, False, True, 0, False, False),      # K = 24 (one stage + a half stage), M = 144 on 192-row tiles
+    (32, 40, 16, 16, 240, False, True, 0, False, False),     # short reduction (K = 40 = a 32-channel stage + a half stage of 8), 64 x 128 tiles (256 items), statistics
+    (8, 24, 32, 32, 144, False, True, 0, False, False),      # K = 24 (one 16-channel stage + a half stage), M = 144 on three 64-row tiles x 128 pixels
     (32, 176, 16, 16, 1056, False, True, 0, False, True),    # the 16x16 expand conv: 192 x 64 tiles in three whole rounds, no split (K = 176 < 8 chunks x 4)
     (32, 1824, 8, 8, 304, False, False, 1, False, True),     # deep data gradient over 2,048 pixels: 320 x 64 tiles, K cut 8 ways, the accumulate is applied by the reduce tail
     (32, 1824, 8, 8, 304, False, True, 0, False, True),      # the same layer forward-shaped: 320 x 64 tiles, K cut 8 ways (balanced partition), statistics in the reduce tail
-    (32, 3072, 8, 8, 512, True, False, 0, False, True),      # 256-row tiles x 2, K cut, bias applied by the reduce tail
+    (32, 3072, 8, 8, 512, True, False, 0, False, True),      # 64 x 64 tiles: 256 items fill the chip, so K is not cut; bias prefetched (what each row reaches: tests/conv_dispatch.py)
     (5, 100, 10, 10, 72, True, True, 0, False, False),       # HW = 100: tiles straddle images, ragged last tile, K tail of 4 channels
     (3, 52, 1, 52, 96, True, False, 1, True, False),         # a Linear over 52-token rows (H = 1): bias + residual + accumulate, all prefetched
     (2, 768, 1, 200, 768, True, False, 0, True, True),       # ViT proj Linear: residual stream, few tokens -> K cut
@@ -523,7 +542,7 @@ CONV3X3_PC = [   # (..., expected kernel family)
 def test_conv3x3_producer_consumer(B, C1, C2, H, W, M, pro, beta, want):
     """launch_conv_pc's 3x3 geometries: (R, XW) by the map width, taken when m-tiles x pixel tiles >= 160 (thin: >= 512 tiles);
     each geometry also at a batch size just below that, which must stay on the generic kernel"""
-    # (statistics + accumulate never occur together in a plan; the oracle takes the statistics before the accumulate)
+    # (statistics + accumulate never occur together in a plan; tests/test_conv_kernels_gpu.py has the rows that combine them)
     _conv_case(B, C1, C2, H, W, M, 3, 1, 1, 1, H, W, pro, pro if C2 else 0, False, bias=True, stats=(beta == 0), beta=beta, want_variant=want)
 
 
