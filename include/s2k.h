@@ -109,6 +109,29 @@ int s2k_program_profile_variants(const S2kOp* ops, int begin, int end, void* con
 int s2k_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                   double eps, double weight_decay, int step, void* stream);
 
+/* MAE reconstruction pictures (render.mae_panels; csrc/mae_render.hip): up to four uint8 panels of what a masked autoencoder made of
+ * a crop, and the per-patch squared error, in ONE launch on `stream`.  A plain function like s2k_adam_step, not a stage kind: it is
+ * never part of a program (nothing plans it, nothing profiles it per kind), and the stage table is frozen at 55 kinds - bindings and
+ * tests enumerate it - so a picture for people does not get to renumber it.  Adding a function leaves S2K_ABI_VERSION at 2.
+ *
+ * Geometry (MaeSpec): C channels, T frames, H == W, patch P | H, tubelet TUB | T; g = H / P, L = (T / TUB) * g * g patches of
+ * PD = TUB * P * P * C features in (tt, py, px, c) order.  Device pointers, borrowed:
+ *   imgs   f32 [B][C][T][H][W]   what the model consumed          pred   f32 [B][L][PD]   MaskedAutoencoderViT.forward's
+ *   mask   f32 [B][L]            non-zero = removed               norm   f32 [2][C]       {mean * 255, 1 / (std * 255)} (TILE_PREP's NORM)
+ *   bounds f64 [B][2]            (lo, hi) of the stretch          out    u8  [B][n_panels][H][W][3]   h w rgb
+ *   patch_mse f32 [B][L] or NULL: mean over PD of (pred - target)^2, target standardised per patch when norm_pix
+ * Host values: bands[3] distinct in [0, C); frame in [0, T); panels[n_panels], 1 <= n_panels <= 4, codes 0 original, 1 masked (removed
+ * patches = `fill`, 0..255), 2 pasted (pred in removed patches, imgs elsewhere), 3 reconstruction; norm_pix 0 or 1 (pred is
+ * de-standardised with the patch's mean and unbiased variance, in f64).
+ * Pixel: v = x / norm[1][c] + norm[0][c]; out = (uint8) trunc(clip((v - lo) / (hi - lo) * 255, 0, 255)) in f64, as TILE_QUICKLOOK;
+ * bounds without a range (hi <= lo, non-finite) and NaN give 0.
+ * Every argument is validated on the host before anything is launched: S2K_EFAULT for a NULL required pointer, S2K_EINVAL for a
+ * dimension, band, frame, fill or panel code out of range, for B or T / TUB above 65535 (grid dimensions) and for C*T*H*W or
+ * n_panels*H*W*3 of 2^31 or more (32-bit offsets inside a sample).  No allocation, no copy, no synchronisation. */
+int s2k_mae_panels(const float* imgs, const float* pred, const float* mask, const float* norm, const double* bounds, unsigned char* out,
+                   float* patch_mse, int B, int C, int T, int H, int W, int P, int TUB, const int* bands, int frame, const int* panels,
+                   int n_panels, int fill, int norm_pix, void* stream);
+
 /* Measured ceilings of the current device for roofline reporting (bench.py): sustained v_mfma_f32_32x32x2_f32 rate with every
  * SIMD issuing back to back (TFLOP/s), the shader clock held meanwhile (MHz), and a float4 stream copy (GB/s, read + write).
  * `scratch`: >= 64 MiB of device memory (size the copy past the caches: 1 GiB+).  Synchronises `stream`.  Not on the hot path. */

@@ -55,6 +55,8 @@ def lib() -> ctypes.CDLL:
     L.s2k_measure_peaks.argtypes = [vp, ctypes.c_size_t, i32, vp, vp, vp, vp]
     L.s2k_selftest_mfma.restype = i32
     L.s2k_selftest_mfma.argtypes = [vp, vp, vp, vp]
+    L.s2k_mae_panels.restype = i32
+    L.s2k_mae_panels.argtypes = [vp] * 7 + [i32] * 7 + [vp, i32, vp, i32, i32, i32, vp]
     if L.s2k_abi_version() != 2:
         raise S2kError(f"libs2k ABI {L.s2k_abi_version()} != 2")
     if L.s2k_op_size() != D.OP_BYTES or OP_DTYPE.itemsize != D.OP_BYTES:
@@ -153,3 +155,19 @@ def measure_peaks(device=None, waves_per_simd: int = 1, scratch_gib: float = 2.0
         check(lib().s2k_measure_peaks(buf.data_ptr(), buf.numel(), waves_per_simd, addr, addr + 8, addr + 16,
                                       torch.cuda.current_stream(dev).cuda_stream))
     return {"mfma_f32_tflops": out[0], "mfma_clock_mhz": out[1], "copy_gbps": out[2]}
+
+
+MAE_PANELS = {"original": 0, "masked": 1, "pasted": 2, "reconstruction": 3}      # panel codes of s2k_mae_panels (include/s2k.h)
+
+
+def mae_panels(imgs, pred, mask, norm, bounds, out, patch_mse, dims, bands, frame: int, panels, fill: int, norm_pix: bool,
+               stream: int) -> int:
+    """s2k_mae_panels (include/s2k.h) as it is: tensors (or None) for the seven pointers, dims = (B, C, T, H, W, P, TUB), `bands`
+    three ints, `panels` panel codes.  Returns the library's code; `check` turns it into S2kError.  The library validates every
+    argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    pl = [] if panels is None else [int(c) for c in panels]
+    b3 = None if bands is None else (ctypes.c_int * 3)(*[int(b) for b in bands])
+    pn = None if panels is None else (ctypes.c_int * max(len(pl), 4))(*pl)
+    return lib().s2k_mae_panels(ptr(imgs), ptr(pred), ptr(mask), ptr(norm), ptr(bounds), ptr(out), ptr(patch_mse), *[int(d) for d in dims],
+                                b3, int(frame), pn, len(pl), int(fill), int(norm_pix), stream)

@@ -84,6 +84,10 @@ int launch_class_overlay(const S2kOp&, const Ctx&);
 int launch_dw_bwd_chain(const S2kOp*, const Ctx&);
 int launch_adam(float*, const float*, float*, float*, int64_t, double, double, double, double, double, int, hipStream_t);
 int launch_mfma_selftest(const float*, const float*, float*, hipStream_t);
+int check_mae_panels(const float*, const float*, const float*, const float*, const double*, unsigned char*, float*, int, int, int, int,
+                     int, int, int, const int*, int, const int*, int, int, int);
+int launch_mae_panels(const float*, const float*, const float*, const float*, const double*, unsigned char*, float*, int, int, int, int,
+                      int, int, int, const int*, int, const int*, int, int, int, hipStream_t);
 
 static int launch_memset(const S2kOp& op, const Ctx& c) {
     const int64_t ref = op.t[S2K_MEMSET_T_DST];
@@ -443,6 +447,22 @@ int s2k_adam_step(float* p, const float* g, float* m, float* v, int64_t n, doubl
     if (rc != S2K_OK) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("adam: %s", hipGetErrorString(e)); return S2K_EHIP; }
+    return S2K_OK;
+}
+
+int s2k_mae_panels(const float* imgs, const float* pred, const float* mask, const float* norm, const double* bounds, unsigned char* out,
+                   float* patch_mse, int B, int C, int T, int H, int W, int P, int TUB, const int* bands, int frame, const int* panels,
+                   int n_panels, int fill, int norm_pix, void* stream) {
+    // every argument is validated before the first HIP call (the device guard's included)
+    const int bad = check_mae_panels(imgs, pred, mask, norm, bounds, out, patch_mse, B, C, T, H, W, P, TUB, bands, frame, panels, n_panels,
+                                     fill, norm_pix);
+    if (bad != S2K_OK) return bad;
+    DeviceGuard guard(static_cast<hipStream_t>(stream));
+    const int rc = launch_mae_panels(imgs, pred, mask, norm, bounds, out, patch_mse, B, C, T, H, W, P, TUB, bands, frame, panels, n_panels,
+                                     fill, norm_pix, static_cast<hipStream_t>(stream));
+    if (rc != S2K_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("mae_panels: %s", hipGetErrorString(e)); return S2K_EHIP; }
     return S2K_OK;
 }
 

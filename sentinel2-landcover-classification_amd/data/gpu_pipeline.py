@@ -279,6 +279,26 @@ class GpuTilePipeline:
         return QL.run_zero_count(self.raw, idx, b).cpu().double() / float(H * W)
 
     @torch.no_grad()
+    def stretch_bounds(self, params, bands=(2, 1, 0), percentile: float = 98.0) -> torch.Tensor:
+        """float64 [B, 2] on the device: for every row of `params` ({tile, y0, x0, flips}) the bounds (lo, hi) between which
+        `quicklook(params=params, bands=bands, percentile=percentile)` stretches that row's picture - the percentiles
+        (100 - percentile, percentile) over the three bands of the row's WHOLE tile, i.e. `band_percentiles([100 - p, p], tiles,
+        bands, pooled=False)` gathered per sample.  Every distinct tile is selected once.  They put other pictures of the same crops
+        (`render.mae_panels`) on the quicklook's colour scale."""
+        N, C, H, W = self._loaded_shape()
+        bl = QL.check_bands(bands, C, count=3)
+        p = QL.check_percentile(percentile)
+        if params is None:
+            raise ValueError("params must be an integer array [B, 4] = {tile, y0, x0, flips}")
+        par = QL.check_params(params, N, H, W, self.S, self.S)
+        if not self.raw.is_cuda:
+            raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
+        tiles, slot = torch.unique(par[:, 0], return_inverse=True)
+        ranks, frac = QL.rank_plan([100.0 - p, p], 3 * H * W)
+        pct = QL.run_selection(self.raw, tiles.to(torch.int32), bl, False, ranks, frac)[1]
+        return pct.index_select(0, slot.to(self.device))
+
+    @torch.no_grad()
     def quicklook(self, indices=None, params=None, bands=(2, 1, 0), percentile: float = 98.0, whole_tile: bool = False) -> torch.Tensor:
         """uint8 [B, S, S, 3] (h w rgb) on the device: the reference's percentile-stretched picture of `bands` for every sample -
         the crop `params` names (the same {tile, y0, x0, flips} array given to `__call__`: the picture is what the model saw), or
