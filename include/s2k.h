@@ -132,6 +132,33 @@ int s2k_mae_panels(const float* imgs, const float* pred, const float* mask, cons
                    float* patch_mse, int B, int C, int T, int H, int W, int P, int TUB, const int* bands, int frame, const int* panels,
                    int n_panels, int fill, int norm_pix, void* stream);
 
+/* Class-map neighbourhood filters (classmap.py; csrc/classmap.hip): the size x size majority (mode) filter of a class map and the
+ * ignore band around class boundaries, in ONE launch on `stream`.  A plain function like s2k_mae_panels, not a stage kind: the stage
+ * table stays at 55 kinds and S2K_ABI_VERSION at 2.
+ *
+ * src, dst: [M][H][W] class maps, uint8 (`*_bytes` == 1) or int64 (== 8), independently; device pointers, borrowed; dst must not alias
+ * src.  src_lut: int32[256] or NULL, only with a 1-byte src: the class of a pixel is then src_lut[raw] (how the pipeline's resident
+ * labels are read through its label map).  1 <= K <= 32 classes; size odd in 3..15, r = size / 2.  The window of pixel (y, x) is
+ * [y-r, y+r] x [x-r, x+r] clipped to the image: no padding, and maps never see each other.  A pixel whose class lies outside [0, K)
+ * never votes and is copied unchanged (into a 1-byte dst: its low byte).
+ *   mode 0, MAJORITY: classes whose bit is set in `votes` vote, the others count 0; best = the largest count in the window.  The output
+ *     is the centre's class if its own count equals best, or best == 0, or the centre's bit is set in `fixed`; otherwise the LOWEST
+ *     class whose count equals best (the centre wins ties, then the lowest index).  `ignore` is unused.
+ *   mode 1, BOUNDARY: a centre of class c != ignore becomes `ignore` iff its window holds a pixel of a class in [0, K) that is neither c
+ *     nor ignore; everything else is copied (touching only the ignored class is no boundary).  votes and fixed must be 0.
+ * changed: u64 [M] or NULL; changed[m] += pixels of map m whose output class differs from their input class.
+ * hist: u64 [K][K] or NULL; with it labels (u8 [nsrc][H][W]), index (device i32 [M], values in [0, nsrc)) and lut (i32[256]) are
+ * required: hist[t][p] += 1 with t = lut[labels[index[m]][y][x]] and p the output class wherever both lie in [0, K) - WINDOW_BLEND's
+ * HIST (LDS bins per workgroup, one 64-bit atomic per non-zero bin).  Both counters are integer sums: exact.
+ * Every argument is validated on the host before anything is launched: S2K_EFAULT for a NULL src or dst; S2K_EINVAL for a width other
+ * than 1 or 8, src_lut with an 8-byte src, src == dst, K, size, mode, ignore (mode 1) out of range, bits of votes / fixed at K and
+ * above (mode 0) or any set (mode 1), M, H or W below 1, H * W >= 2^31 (offsets inside a map are 32-bit; the map offset is 64-bit),
+ * M * ceil(W / (64 - 2r)) * ceil(H / 16) >= 2^24 (one workgroup per strip and band of a map), hist without labels, index, lut or with
+ * nsrc < 1.  Messages begin with "classmap_filter: ".  No allocation, no copy, no synchronisation. */
+int s2k_classmap_filter(const void* src, int src_bytes, const int* src_lut, void* dst, int dst_bytes, int M, int H, int W, int K,
+                        int size, int mode, unsigned votes, unsigned fixed, int ignore, const unsigned char* labels, const int* index,
+                        const int* lut, int nsrc, unsigned long long* hist, unsigned long long* changed, void* stream);
+
 /* Measured ceilings of the current device for roofline reporting (bench.py): sustained v_mfma_f32_32x32x2_f32 rate with every
  * SIMD issuing back to back (TFLOP/s), the shader clock held meanwhile (MHz), and a float4 stream copy (GB/s, read + write).
  * `scratch`: >= 64 MiB of device memory (size the copy past the caches: 1 GiB+).  Synchronises `stream`.  Not on the hot path. */

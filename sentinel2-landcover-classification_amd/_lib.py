@@ -57,6 +57,9 @@ def lib() -> ctypes.CDLL:
     L.s2k_selftest_mfma.argtypes = [vp, vp, vp, vp]
     L.s2k_mae_panels.restype = i32
     L.s2k_mae_panels.argtypes = [vp] * 7 + [i32] * 7 + [vp, i32, vp, i32, i32, i32, vp]
+    u32 = ctypes.c_uint
+    L.s2k_classmap_filter.restype = i32
+    L.s2k_classmap_filter.argtypes = [vp, i32, vp, vp, i32] + [i32] * 6 + [u32, u32, i32, vp, vp, vp, i32, vp, vp, vp]
     if L.s2k_abi_version() != 2:
         raise S2kError(f"libs2k ABI {L.s2k_abi_version()} != 2")
     if L.s2k_op_size() != D.OP_BYTES or OP_DTYPE.itemsize != D.OP_BYTES:
@@ -155,6 +158,22 @@ def measure_peaks(device=None, waves_per_simd: int = 1, scratch_gib: float = 2.0
         check(lib().s2k_measure_peaks(buf.data_ptr(), buf.numel(), waves_per_simd, addr, addr + 8, addr + 16,
                                       torch.cuda.current_stream(dev).cuda_stream))
     return {"mfma_f32_tflops": out[0], "mfma_clock_mhz": out[1], "copy_gbps": out[2]}
+
+
+CLASSMAP_MODES = {"majority": 0, "boundary": 1}      # modes of s2k_classmap_filter (include/s2k.h)
+
+
+def classmap_filter(src, src_lut, dst, dims, size: int, mode: int, votes: int, fixed: int, ignore: int, labels, index, lut, nsrc: int,
+                    hist, changed, stream: int, src_bytes: int | None = None, dst_bytes: int | None = None) -> int:
+    """s2k_classmap_filter (include/s2k.h) as it is: tensors (or None) for the eight pointers, dims = (M, H, W, K); the element widths
+    default to the tensors' own.  Returns the library's code; `check` turns it into S2kError.  The library validates every argument
+    on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    sb = (8 if src is None else src.element_size()) if src_bytes is None else int(src_bytes)
+    db = (8 if dst is None else dst.element_size()) if dst_bytes is None else int(dst_bytes)
+    return lib().s2k_classmap_filter(ptr(src), sb, ptr(src_lut), ptr(dst), db, *[int(d) for d in dims], int(size), int(mode),
+                                     int(votes) & 0xffffffff, int(fixed) & 0xffffffff, int(ignore), ptr(labels), ptr(index), ptr(lut),
+                                     int(nsrc), ptr(hist), ptr(changed), stream)
 
 
 MAE_PANELS = {"original": 0, "masked": 1, "pasted": 2, "reconstruction": 3}      # panel codes of s2k_mae_panels (include/s2k.h)

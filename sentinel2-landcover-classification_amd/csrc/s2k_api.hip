@@ -88,6 +88,10 @@ int check_mae_panels(const float*, const float*, const float*, const float*, con
                      int, int, int, const int*, int, const int*, int, int, int);
 int launch_mae_panels(const float*, const float*, const float*, const float*, const double*, unsigned char*, float*, int, int, int, int,
                       int, int, int, const int*, int, const int*, int, int, int, hipStream_t);
+int check_classmap_filter(const void*, int, const int*, void*, int, int, int, int, int, int, int, unsigned, unsigned, int, const unsigned char*,
+                          const int*, const int*, int, unsigned long long*, unsigned long long*);
+int launch_classmap_filter(const void*, int, const int*, void*, int, int, int, int, int, int, int, unsigned, unsigned, int, const unsigned char*,
+                           const int*, const int*, int, unsigned long long*, unsigned long long*, hipStream_t);
 
 static int launch_memset(const S2kOp& op, const Ctx& c) {
     const int64_t ref = op.t[S2K_MEMSET_T_DST];
@@ -463,6 +467,22 @@ int s2k_mae_panels(const float* imgs, const float* pred, const float* mask, cons
     if (rc != S2K_OK) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("mae_panels: %s", hipGetErrorString(e)); return S2K_EHIP; }
+    return S2K_OK;
+}
+
+int s2k_classmap_filter(const void* src, int src_bytes, const int* src_lut, void* dst, int dst_bytes, int M, int H, int W, int K, int size,
+                        int mode, unsigned votes, unsigned fixed, int ignore, const unsigned char* labels, const int* index, const int* lut,
+                        int nsrc, unsigned long long* hist, unsigned long long* changed, void* stream) {
+    // every argument is validated before the first HIP call (the device guard's included)
+    const int bad = check_classmap_filter(src, src_bytes, src_lut, dst, dst_bytes, M, H, W, K, size, mode, votes, fixed, ignore, labels, index,
+                                          lut, nsrc, hist, changed);
+    if (bad != S2K_OK) return bad;
+    DeviceGuard guard(static_cast<hipStream_t>(stream));
+    const int rc = launch_classmap_filter(src, src_bytes, src_lut, dst, dst_bytes, M, H, W, K, size, mode, votes, fixed, ignore, labels, index,
+                                          lut, nsrc, hist, changed, static_cast<hipStream_t>(stream));
+    if (rc != S2K_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("classmap_filter: %s", hipGetErrorString(e)); return S2K_EHIP; }
     return S2K_OK;
 }
 

@@ -31,6 +31,7 @@ import typing
 import numpy as np
 import torch
 
+from .. import classmap as CM
 from ..plan import opdefs as D
 from . import dataset_stats as DS
 from . import quicklook as QL
@@ -92,7 +93,9 @@ class GpuTilePipeline:
         m *= np.float32(max_pixel_value)
         s *= np.float32(max_pixel_value)
         self.norm = torch.from_numpy(np.stack([m, np.reciprocal(s, dtype=np.float32)])).to(self.device)
-        self.lut = label_lut(label_map).to(self.device)
+        lut = label_lut(label_map)
+        self.label_classes = int(lut.max()) + 1      # of the label map: what `ignore_label_boundaries` filters over
+        self.lut = lut.to(self.device)
         self.raw = self.labels = None
         if self.S % 4:
             raise ValueError("random_crop_size must be a multiple of 4")
@@ -236,6 +239,33 @@ class GpuTilePipeline:
         """float32 CPU tensor [M]: the reference's `get_sample_weights` for the selected tiles, in their order."""
         K = len(torch.as_tensor(class_distribution).reshape(-1))
         return DS.sample_weights_from_hist(self.label_histogram(K, indices, window).cpu(), class_distribution, ignore_zero_label)
+
+    @torch.no_grad()
+    def ignore_label_boundaries(self, size: int = 3, ignore_index: int = 0) -> None:
+        """Rewrite the resident labels ONCE so that a band around class boundaries is ignored: the new labels are
+        `classmap.boundary_to_ignore(lut[labels], num_classes, size, ignore_index)` stored as uint8 CLASSES (no longer raw codes), and
+        the pipeline's label table becomes the identity - TILE_PREP's `y`, `label_histogram`, `class_probabilities`, `sample_weights`
+        and `TilePredictor.evaluate` then see the band as class `ignore_index` with no further change.  Rasterised polygon labels are
+        wrong by a pixel or so wherever two classes meet; with the reference's `masked_loss` convention (class 0 ignored) the default
+        takes those pixels out of loss, metrics and sampling weights.  `num_classes` is the label map's: its largest class + 1.
+        Both tensors are REPLACED, not written (load() may have kept the caller's own label tensor): the packed TILE_PREP call binds
+        its tensors anew at every use (`stage_call.cached`), and every other call over them is built per use, so none serves the old
+        ones.  One launch; after a second call the band is that of the already banded labels."""
+        size = CM.check_size(size)
+        if self.raw is None:
+            raise RuntimeError("call load() first")
+        if self.labels is None:
+            raise ValueError("the pipeline was loaded without labels")
+        if self.label_classes > CM.MAX_CLASSES:
+            raise ValueError(f"the label map has {self.label_classes} classes: boundaries are marked for at most {CM.MAX_CLASSES}")
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not 0 <= ignore_index < self.label_classes:
+            raise ValueError(f"ignore_index must be a class id in [0, {self.label_classes})")
+        if not self.labels.is_cuda:
+            raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
+        new = torch.empty_like(self.labels)
+        CM.launch(self.labels, new, self.label_classes, size, CM.BOUNDARY, ignore=ignore_index, src_lut=self.lut)
+        self.labels = new
+        self.lut = torch.arange(256, dtype=torch.int32).to(self.device)
 
     def weighted_indices(self, weights, num_samples: int, generator: torch.Generator | None = None) -> torch.Tensor:
         """int64 [num_samples] positions drawn with replacement in proportion to `weights`, on the host: exactly what

@@ -11,6 +11,7 @@ a gather with a fixed summation order, so a prediction is bit-identical from run
     class_map = predictor.predict([3, 17])                              # int64 [2, H, W] on the device
     predictor.evaluate(metrics)                                         # whole-tile confusion counts into metrics.hist
     metrics.compute()                                                   # whole-tile IoU / accuracy / F1
+    class_map = predictor.predict([3, 17], majority=5)                  # after the 5 x 5 majority filter (classmap.py); so evaluate, render
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ import math
 
 import torch
 
+from . import classmap as CM
 from .data import quicklook as QL
 from .render import overlay
 from .stage_call import StageCall
@@ -102,31 +104,52 @@ class TilePredictor:
         self.profile = window_profile(self.S, window)
 
     # ---- public surface ------------------------------------------------------------------------------------------------------
-    def predict(self, indices=None) -> torch.Tensor:
-        """int64 [M, H, W] on the device: the class of every pixel of the selected tiles (None = every resident tile)."""
-        return self._run(indices, want="mask")
+    def predict(self, indices=None, majority: int | None = None, iterations: int = 1) -> torch.Tensor:
+        """int64 [M, H, W] on the device: the class of every pixel of the selected tiles (None = every resident tile).  majority=k:
+        after `iterations` passes of the k x k majority filter (`classmap.majority_filter`: every class votes, none is fixed)."""
+        if majority is None:
+            return self._run(indices, want="mask")
+        size, its = CM.check_size(majority), CM.check_iterations(iterations)
+        return CM.run_majority(self._run(indices, want="mask"), self.K, size, its, CM.class_bits(None, self.K, "votes"), 0)
 
     def predict_blend(self, indices=None) -> torch.Tensor:
         """float32 [M, K, H, W] on the device: the blended probabilities (blend="probs") or logits."""
         return self._run(indices, want="blend")
 
-    def evaluate(self, metrics, indices=None) -> None:
+    def evaluate(self, metrics, indices=None, majority: int | None = None, iterations: int = 1) -> None:
         """Add the whole-tile confusion counts of the selected tiles - hist[true][predicted] against the pipeline's resident labels
-        after its label map - into `metrics.hist` (a `metrics.SegMetrics`), inside the blending launch itself."""
+        after its label map - into `metrics.hist` (a `metrics.SegMetrics`), inside the blending launch itself.  majority=k: the counts
+        of the map after `iterations` passes of the k x k majority filter, added by the last filter launch (no separate CONFUSION
+        pass, no int64 label tensor)."""
         if int(metrics.C) != self.K:
             raise ValueError("metrics.num_classes differs from the predictor's")
-        self._run(indices, want="hist", metrics=metrics)
+        if majority is None:
+            self._run(indices, want="hist", metrics=metrics)
+            return
+        size, its = CM.check_size(majority), CM.check_iterations(iterations)
+        pipe = self.pipe
+        if pipe.raw is None:
+            raise RuntimeError("call load() first")
+        idx = pipe._stats_index(indices, need_labels=True)               # ValueError first, then the refusal to run off the GPU
+        mask = self._run(idx, want="mask")
+        if metrics.hist.device != pipe.device:
+            metrics.hist = metrics.hist.to(pipe.device)
+        CM.run_majority(mask, self.K, size, its, CM.class_bits(None, self.K, "votes"), 0,
+                        last=(pipe.labels, idx.to(pipe.device), pipe.lut, metrics.hist))
 
-    def render(self, indices, palette, alpha: float = 0.5) -> torch.Tensor:
+    def render(self, indices, palette, alpha: float = 0.5, majority: int | None = None, iterations: int = 1) -> torch.Tensor:
         """uint8 [M, H, W, 3] on the device: the whole-tile quicklook of the selected tiles (`GpuTilePipeline.quicklook`, its default
-        bands and percentile) with the predicted class map laid over it in the colours of `palette` (uint8 [>= num_classes, 3]) at
-        opacity `alpha` (`render.overlay`)."""
+        bands and percentile) with the predicted class map (`predict(indices, majority, iterations)`) laid over it in the colours of
+        `palette` (uint8 [>= num_classes, 3]) at opacity `alpha` (`render.overlay`)."""
+        if majority is not None:
+            CM.check_size(majority)
+            CM.check_iterations(iterations)
         pal = QL.check_palette(palette)
         QL.alpha_code(alpha)
         if pal.shape[0] < self.K:
             raise ValueError("palette needs one colour per class")
         picture = self.pipe.quicklook(indices, whole_tile=True)          # ValueError first, then the refusal to run off the GPU
-        return overlay(picture, self.predict(indices), pal, alpha)
+        return overlay(picture, self.predict(indices, majority, iterations), pal, alpha)
 
     # ---- implementation ------------------------------------------------------------------------------------------------------
     def _geometry(self):
