@@ -27,9 +27,10 @@ class Mem:
     checks the planner's algebra to ~1e-12, free of the fp32 noise that small-batch BatchNorm
     and ReLU masks amplify to ~1e-2 in the gradients."""
 
-    def __init__(self, bases: dict[int, torch.Tensor], wide: bool = False, narrow_bases=()):
+    def __init__(self, bases: dict[int, torch.Tensor], wide: bool = False, narrow_bases=(), b16_operands: bool = False):
         self.bases = bases
         self.wide = wide
+        self.b16 = bool(b16_operands)     # wide only: FLAG_BF16 stages round their operands as the kernels do (see _bf16_operands)
         self.narrow = set(narrow_bases)
         self.fdtype = torch.float64 if wide else torch.float32
 
@@ -125,8 +126,18 @@ def op_weight_pack(m: Mem, o):
 def _bf16_operands(m: Mem, o) -> bool:
     """bf16-MIXED stage (S2kOp.flags & FLAG_BF16): the two MFMA operands - the activated inputs and the weights - are rounded to
     bf16 (round-to-nearest-even), products and sums stay f32.  Not applied in `wide` (float64) emulation: that mode checks the
-    planner's algebra, not the arithmetic."""
-    return bool(o.get("_flags", 0) & 4) and not m.wide
+    planner's algebra, not the arithmetic - unless run_program is given b16_operands=True, the float64 reference OF the bf16
+    operation: the prologue is evaluated in f32 as the kernels do (_pro_b16), the activated operand and the weight are rounded to
+    bf16, and the products, the sums, the epilogue terms and the statistics are float64."""
+    return bool(o.get("_flags", 0) & 4) and (not m.wide or m.b16)
+
+
+def _pro_b16(m: Mem, o, x, bnv, gate, pro, C):
+    """_pro; in the float64 reference of a bf16 stage (wide + b16_operands) evaluated in f32, as the kernels evaluate it"""
+    if m.wide and _bf16_operands(m, o):
+        f = lambda t: None if t is None else t.float()     # noqa: E731  (the tensors hold f32 values: exact)
+        return _pro(f(x), f(bnv), f(gate), pro, C).double()
+    return _pro(x, bnv, gate, pro, C)
 
 
 def _r16(t: torch.Tensor) -> torch.Tensor:
@@ -143,9 +154,9 @@ def op_conv(m: Mem, o):
         x1 = _unshuffle2(m.view(o["X1"], (B, co, 2 * H, 2 * W)))
     else:
         x1 = m.view(o["X1"], (B, C1, H, W), "bf16" if o.get("X1_BF16", 0) else "f32").to(m.fdtype)
-    x = _pro(x1, m.view(o["BNV1"], (4, C1)), m.view(o["GATE1"], (B, C1)), o["PRO1"], C1)
+    x = _pro_b16(m, o, x1, m.view(o["BNV1"], (4, C1)), m.view(o["GATE1"], (B, C1)), o["PRO1"], C1)
     if C2:
-        x2 = _pro(m.view(o["X2"], (B, C2, H, W)), m.view(o["BNV2"], (4, C2)), None, o["PRO2"], C2)
+        x2 = _pro_b16(m, o, m.view(o["X2"], (B, C2, H, W)), m.view(o["BNV2"], (4, C2)), None, o["PRO2"], C2)
         x = torch.cat([x, x2], 1)
     wv = m.view(o["WT"], (M, Ct, T), strides=(o["W_SM"], o["W_SK"], o["W_ST"]))
     if o["FLIP"]:
@@ -187,8 +198,8 @@ def op_wgrad(m: Mem, o):
     B, M, C, CT, H, W = o["B"], o["M"], o["C"], o["CTOT"], o["H"], o["W"]
     KH, KW, S, Ho, Wo, mode = o["KH"], o["KW"], o["STRIDE"], o["HO"], o["WO"], o["MODE"]
     T = KH * KW
-    P = _pro(m.view(o["P"], (B, M, Ho, Wo), "bf16" if o.get("P_BF16", 0) else "f32").to(m.fdtype), m.view(o["BNVP"], (4, M)), m.view(o["GATEP"], (B, M)), o["PROP"], M)
-    Q = _pro(m.view(o["Q"], (B, C, H, W)), m.view(o["BNVQ"], (4, C)), m.view(o["GATEQ"], (B, C)), o["PROQ"], C)
+    P = _pro_b16(m, o, m.view(o["P"], (B, M, Ho, Wo), "bf16" if o.get("P_BF16", 0) else "f32").to(m.fdtype), m.view(o["BNVP"], (4, M)), m.view(o["GATEP"], (B, M)), o["PROP"], M)
+    Q = _pro_b16(m, o, m.view(o["Q"], (B, C, H, W)), m.view(o["BNVQ"], (4, C)), m.view(o["GATEQ"], (B, C)), o["PROQ"], C)
     if _bf16_operands(m, o):
         P, Q = _r16(P), _r16(Q)
     if mode == 2:
@@ -866,8 +877,11 @@ def unpack(packed: np.ndarray, opdefs) -> list[tuple[str, dict]]:
 
 
 def run_program(packed: np.ndarray, bases: dict[int, torch.Tensor], opdefs, wide: bool = False,
-                narrow_bases=()) -> None:
-    m = Mem(bases, wide, narrow_bases)
+                narrow_bases=(), b16_operands: bool = False) -> None:
+    """b16_operands (with wide; no existing caller passes it): FLAG_BF16 stages become the float64 reference of the bf16 operation
+    (_bf16_operands) instead of the unrounded float64 emulation; every other stage, and every call without it, is unchanged."""
+    assert wide or not b16_operands
+    m = Mem(bases, wide, narrow_bases, b16_operands)
     with torch.no_grad():
         for kind, o in unpack(packed, opdefs):
             if kind in ("DWCONV_DGRAD", "DWCONV_WGRAD", "LOSS_BWD"):

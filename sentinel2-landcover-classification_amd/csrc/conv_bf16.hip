@@ -630,13 +630,14 @@ static int conv_b16_route(ConvP& p, hipStream_t st) {
         // (measured: 8 x 8 / 16 x 16 maps 43 -> 22 us, 34 -> 18, 20 -> 10; large pixel counts are matrix-core / bandwidth-bound and lose
         // 4 - 8 % to the larger LDS image, so only problems of at most 1,024 128 x 128 tiles take it; the 32-row tile would spill)
         const bool deep = p.Ctot >= deep_min && p.M > 32 && (int64_t)cdiv(p.Ntot, 128) * cdiv(p.M, 128) <= 1024;
+        if (!SPLIT && p.x1_bf16) {      // X1 stored as bf16 (opdefs CONV.X1_BF16): planned only for this shape class; nothing else reads such a tensor
+            // (before the gated form: a gated SiLU stage would otherwise read the halves as floats)
+            if (p.gate1 || p.pro1 != S2K_PRO_NONE || (p.HW & 7)) { set_error("conv: X1_BF16 is for plain 1x1 stages (no prologue, H*W % 8 == 0)"); return S2K_EINVAL; }
+            if constexpr (!SPLIT) return deep ? launch_b16_pix<128, S2K_PRO_NONE, false, true>(p, st) : launch_b16_pix<64, S2K_PRO_NONE, false, true>(p, st);
+        }
         if (p.gate1) {
             if (p.pro1 == S2K_PRO_SILU) return deep ? launch_b16_pix<KDEEP, S2K_PRO_SILU, true, false, SPLIT>(p, st) : launch_b16_pix<K1, S2K_PRO_SILU, true, false, SPLIT>(p, st);
             return 1;
-        }
-        if (!SPLIT && p.x1_bf16) {      // X1 stored as bf16 (opdefs CONV.X1_BF16): planned only for this shape class; nothing else reads such a tensor
-            if (p.gate1 || p.pro1 != S2K_PRO_NONE || (p.HW & 7)) { set_error("conv: X1_BF16 is for plain 1x1 stages (no prologue, H*W % 8 == 0)"); return S2K_EINVAL; }
-            if constexpr (!SPLIT) return deep ? launch_b16_pix<128, S2K_PRO_NONE, false, true>(p, st) : launch_b16_pix<64, S2K_PRO_NONE, false, true>(p, st);
         }
         switch (p.pro1) {
             case S2K_PRO_NONE: return deep ? launch_b16_pix<KDEEP, S2K_PRO_NONE, false, false, SPLIT>(p, st) : launch_b16_pix<K1, S2K_PRO_NONE, false, false, SPLIT>(p, st);

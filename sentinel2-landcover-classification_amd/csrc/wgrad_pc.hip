@@ -359,6 +359,7 @@ static int launch_pc2(WgradP& p, hipStream_t st) {
 
 template <int R, int XWE>
 static int launch_pc_spatial(WgradP& p, hipStream_t st) {
+    if (p.prop != S2K_PRO_NONE) return 1;       // no 3x3 form has a prologue on P: the generic launcher reports the record
     if (p.proq == S2K_PRO_NONE) return launch_pc2<WG_SPATIAL, 9, 1, 1, 2, 2, 1, 64, R, XWE, S2K_PRO_NONE, S2K_PRO_NONE>(p, st);
     if (p.proq == S2K_PRO_RELU) return launch_pc2<WG_SPATIAL, 9, 1, 1, 2, 2, 1, 64, R, XWE, S2K_PRO_NONE, S2K_PRO_RELU>(p, st);
     return 1;
@@ -367,6 +368,7 @@ static int launch_pc_spatial(WgradP& p, hipStream_t st) {
 // thin layers (a 32-channel side): 128-pixel tiles (2 rows x 64), the four consumer waves split the pixel pairs
 template <int WVM>
 static int launch_pc_spatial_thin(WgradP& p, hipStream_t st) {
+    if (p.prop != S2K_PRO_NONE) return 1;
     if (p.proq == S2K_PRO_NONE) return launch_pc2<WG_SPATIAL, 9, 1, 1, WVM, 1, 4 / WVM, 128, 2, 64, S2K_PRO_NONE, S2K_PRO_NONE>(p, st);
     if (p.proq == S2K_PRO_RELU) return launch_pc2<WG_SPATIAL, 9, 1, 1, WVM, 1, 4 / WVM, 128, 2, 64, S2K_PRO_NONE, S2K_PRO_RELU>(p, st);
     return 1;

@@ -7,7 +7,7 @@ conv_igemm_kernel - at their default tuning (tune_int defaults, listed below) an
 
 The keyword arguments are the CONV record's fields (opdefs.OPS["CONV"]) that decide the routing; tensors are given as truth values
 (GATE, BIAS, RES, STATS, SCRATCH).  `flags` takes FLAG_Q4 / FLAG_DMA / FLAG_RES_GELU_GRAD; FLAG_BF16, FLAG_SPLIT and X1_BF16 belong
-to csrc/conv_bf16.hip and raise NotImplementedError.  Besides the kernel family (the code the launcher leaves in g_s2k_variant:
+to csrc/conv_bf16.hip (tests/b16_dispatch.py restates it) and raise NotImplementedError.  Besides the kernel family (the code the launcher leaves in g_s2k_variant:
 0 generic, 1 producer / consumer, 3 LDS-DMA ring, 4 quad reads) and the exact template instantiation, a Cv holds the run-time facts
 a test case has to reach: tile counts and ragged edges, the split-K partition, the epilogue form, the K tail, tiles that straddle
 images, the 3x3 tiling, the persistent kernels' items per workgroup.  The two cost searches are restated in the launchers' own
@@ -555,7 +555,7 @@ def dispatch(*, B, C1, H, W, M, C2=0, KH=1, KW=1, STRIDE=1, PAD_T=0, PAD_L=0, HO
              X1_BF16=0, flags=0) -> Cv:
     """launch_conv (csrc/igemm.hip) on one CONV record.  ValueError where the launcher reports S2K_EINVAL."""
     if flags & (FLAG_BF16 | FLAG_SPLIT) or X1_BF16:
-        raise NotImplementedError("FLAG_BF16 / FLAG_SPLIT / X1_BF16 stages belong to csrc/conv_bf16.hip")
+        raise NotImplementedError("FLAG_BF16 / FLAG_SPLIT / X1_BF16 stages belong to csrc/conv_bf16.hip: tests/b16_dispatch.conv restates its launchers")
     p = _P()
     p.B, p.C1, p.C2, p.H, p.W, p.M, p.KH, p.KW, p.S, p.PT, p.PL = B, C1, C2, H, W, M, KH, KW, STRIDE, PAD_T, PAD_L
     p.HO, p.WO = (H if HO is None else HO), (W if WO is None else WO)

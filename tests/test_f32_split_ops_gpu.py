@@ -159,7 +159,7 @@ def _wgrad(B, M, C, CT, c_off, H, W, k, prop, proq, gateq, seed=0):
 
 
 @pytest.mark.parametrize("B,C1,H,W,M,pro,gate,bias,stats,beta", [
-    (3, 24, 16, 16, 144, 0, False, False, True, 0),     # short K (24 of a 32-channel chunk), 128-row tiles
+    (3, 24, 16, 16, 144, 0, False, False, True, 0),     # short K (24 of a 32-channel chunk); 64 x 64 tiles (fewer than 200 tiles of 128 x 128)
     (2, 144, 16, 16, 40, 2, True, False, True, 0),      # project conv: BatchNorm + SiLU + SE gate prologue, 64-row tiles
     (2, 40, 12, 20, 240, 0, False, False, True, 0),
     (2, 1824, 8, 8, 304, 2, True, False, True, 0),      # deep project conv: 64-channel chunks, few pixels
@@ -179,7 +179,7 @@ def test_conv1x1_split(B, C1, H, W, M, pro, gate, bias, stats, beta):
     (4, 32, 24, 64, 128, 64, 0, 0),      # (R, XW) = (2, 64): decoder concat conv, two x tiles per row
     (8, 64, 0, 32, 32, 128, 3, 0),       # (4, 32): BatchNorm + ReLU prologue, zero padding after the activation
     (20, 72, 0, 16, 16, 192, 3, 1),      # (8, 16): K tail, accumulate
-    (4, 24, 0, 30, 56, 72, 0, 0),        # (2, 56), odd row count, K tail
+    (4, 24, 0, 30, 56, 72, 0, 0),        # (2, 56): 15 whole tile rows, K tail
     (12, 32, 0, 28, 28, 64, 3, 0),       # (4, 28)
     (40, 64, 0, 14, 14, 128, 0, 0),      # (8, 14)
     (8, 32, 13, 64, 64, 32, 0, 0),       # thin (M <= 32): concat with the raw 13-band input
@@ -221,7 +221,7 @@ def test_conv_dgrad_3x3_flip_split(beta):
 @pytest.mark.parametrize("B,M,C,H,W,prop,proq,gate", [
     (5, 240, 250, 16, 16, 0, 0, False),      # 128 x 128 tiles, ragged on both sides
     (8, 240, 72, 8, 8, 0, 2, True),          # 128 x 64, SiLU + SE gate on Q
-    (4, 40, 144, 16, 20, 0, 3, False),       # 64 x 128, ReLU on Q
+    (4, 40, 144, 16, 20, 0, 3, False),       # 64 x 64 (three c tiles), ReLU on Q
     (3, 64, 64, 20, 20, 2, 0, False),        # SiLU prologue on P
     (2, 768, 384, 1, 520, 0, 0, False),      # a Linear over feature-major tokens; tiles straddle images
     (4, 130, 130, 16, 16, 3, 0, False),      # ReLU on P
@@ -235,11 +235,11 @@ def test_wgrad_1x1_split(B, M, C, H, W, prop, proq, gate):
 
 @pytest.mark.parametrize("B,M,C,CT,c_off,H,W,proq", [
     (2, 64, 64, 64, 0, 6, 64, 3),        # BatchNorm + ReLU on Q: zero padding after the activation
-    (1, 128, 88, 88, 0, 10, 128, 0),     # two x tiles per row, ragged c tile
+    (1, 128, 88, 88, 0, 10, 128, 0),     # four x tiles per row (2 x 32 pixel tiles), ragged c tile
     (2, 72, 40, 104, 64, 12, 32, 3),     # channel slice of a concat conv (CTOT > C), ragged m / c tiles
     (2, 256, 64, 64, 0, 16, 16, 0),      # 16-wide maps: 4 m-tiles
     (3, 64, 128, 128, 0, 10, 16, 3),     # H not a multiple of the tile height
-    (1, 32, 13, 45, 32, 10, 128, 0),     # 13 of 64 columns used
+    (1, 32, 13, 45, 32, 10, 128, 0),     # 32 x 32 tile: 13 of 32 columns used
     (2, 24, 32, 32, 0, 5, 64, 3),        # 32 x 32 tile, odd height
     (2, 64, 24, 24, 0, 9, 128, 0),       # 64 x 32 tiles
     (2, 32, 64, 64, 0, 8, 64, 3),        # 32 x 64 tiles

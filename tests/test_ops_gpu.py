@@ -397,10 +397,10 @@ def test_bf16_stored_operand_is_refused_by_the_f32_kernels():
 
 # ---- bf16-mixed: the same stage records with FLAG_BF16 (csrc/conv_bf16.hip) -----------------------------------------------------------
 @pytest.mark.parametrize("B,C1,H,W,M,pro,gate,bias,stats,beta", [
-    (3, 24, 16, 16, 144, 0, False, False, True, 0),     # short K (24 of a 64-channel chunk), 128-row tiles
+    (3, 24, 16, 16, 144, 0, False, False, True, 0),     # short K (24 of a 64-channel chunk); 6 x 3 tiles of 128 x 128 < 200: 64 x 64 tiles (tests/b16_dispatch.py)
     (2, 144, 16, 16, 40, 2, True, False, True, 0),      # project conv: BatchNorm + SiLU + SE gate prologue, 64-row tiles
     (2, 40, 12, 20, 240, 0, False, False, True, 0),
-    (2, 1824, 8, 8, 304, 2, True, False, True, 0),      # deep project conv: 29 chunks, few pixels
+    (2, 1824, 8, 8, 304, 2, True, False, True, 0),      # deep project conv: 15 chunks of 128 channels (the last holds 32), few pixels
     (2, 32, 24, 24, 24, 3, False, True, False, 0),      # thin (M <= 32): 1 x 4 waves over 256 pixels, ReLU prologue, bias
     (1, 13, 8, 8, 48, 0, False, False, True, 0),        # K tail (13 channels)
     (4, 264, 64, 64, 200, 3, False, True, True, 0),     # K tail (264 = 4 x 64 + 8), ReLU prologue, bias
@@ -419,7 +419,7 @@ def test_conv1x1_bf16(B, C1, H, W, M, pro, gate, bias, stats, beta):
     (4, 32, 24, 64, 128, 64, 0, 0),      # (R, XW) = (2, 64): decoder concat conv (C1 a multiple of 16), two x tiles per row
     (8, 64, 0, 32, 32, 128, 3, 0),       # (4, 32): BatchNorm + ReLU prologue, zero padding after the activation
     (20, 72, 0, 16, 16, 192, 3, 1),      # (8, 16): K tail (72 = 4 x 16 + 8), accumulate
-    (4, 24, 0, 30, 56, 72, 0, 0),        # (2, 56) (224-pixel inputs), odd row count, K tail
+    (4, 24, 0, 30, 56, 72, 0, 0),        # (2, 56) (224-pixel inputs): 15 whole tile rows, K tail
     (12, 32, 0, 28, 28, 64, 3, 0),       # (4, 28)
     (40, 64, 0, 14, 14, 128, 0, 0),      # (8, 14)
     (8, 32, 13, 64, 64, 32, 0, 0),       # thin (M <= 32): 4 x 64 pixel tiles; concat with the raw 13-band input (K tail in source 2)
@@ -631,12 +631,12 @@ def _wgrad_case(B, M, C, CT, c_off, H, W, k, s, pt, pl, Ho, Wo, prop, proq, gate
 @pytest.mark.parametrize("B,M,C,H,W,prop,proq,gate", [
     (5, 240, 250, 16, 16, 0, 0, False),      # 128 x 128 tiles, ragged on both sides
     (8, 240, 72, 8, 8, 0, 2, True),          # 128 x 64, SiLU + SE gate on Q (a project conv's weight gradient)
-    (4, 40, 144, 16, 20, 0, 3, False),       # 64 x 128 (M = 40: one ragged 64-row tile), ReLU on Q
+    (4, 40, 144, 16, 20, 0, 3, False),       # 64 x 64, three c tiles (144 pads a 128-wide tile by more than 12 %; M = 40: one ragged 64-row tile), ReLU on Q
     (3, 64, 64, 20, 20, 2, 0, False),        # 64 x 64, SiLU prologue on P (ConvTranspose weight gradient)
     (2, 768, 384, 1, 520, 0, 0, False),      # a Linear over feature-major tokens: H = 1, W = tokens; tiles straddle images (520 = 8 x 65)
     (4, 130, 130, 16, 16, 3, 0, False),      # 64-row tiles x 3, ReLU on P
     (2, 24, 4, 64, 64, 0, 3, False),         # thin on both sides: 32 x 32 tile, the waves split 256-pixel tiles
-    (2, 24, 144, 32, 32, 0, 2, True),        # 32 x 128... thin M: 32 x 64 tiles, SiLU + gate on Q
+    (2, 24, 144, 32, 32, 0, 2, True),        # thin M: 32 x 64 tiles, SiLU + gate on Q
     (3, 144, 24, 20, 20, 0, 0, False),       # thin C: 64 x 32 tiles; 400 pixels per image (tiles straddle images)
 ])
 def test_wgrad_1x1_bf16(B, M, C, H, W, prop, proq, gate):
@@ -644,12 +644,12 @@ def test_wgrad_1x1_bf16(B, M, C, H, W, prop, proq, gate):
 
 
 @pytest.mark.parametrize("B,M,C,CT,c_off,H,W,proq", [
-    (2, 64, 64, 64, 0, 6, 64, 3),        # (R, XW) = (2, 64), BatchNorm + ReLU on Q: zero padding after the activation
-    (1, 128, 88, 88, 0, 10, 128, 0),     # (2, 64), two x tiles per row (the halo columns come from the neighbouring tile), ragged c tile
+    (2, 64, 64, 64, 0, 6, 64, 3),        # (R, XW) = (4, 64), BatchNorm + ReLU on Q: zero padding after the activation; partial last tile row
+    (1, 128, 88, 88, 0, 10, 128, 0),     # (4, 64), two x tiles per row (the halo columns come from the neighbouring tile), ragged c tile
     (2, 72, 40, 104, 64, 12, 32, 3),     # (4, 32), channel slice of a concat conv (CTOT > C), ragged m / c tiles
     (2, 256, 64, 64, 0, 16, 16, 0),      # (8, 16): 4 m-tiles
     (3, 64, 128, 128, 0, 10, 16, 3),     # (8, 16), H not a multiple of R
-    (1, 32, 13, 45, 32, 10, 128, 0),     # 13 of 64 columns used, channel slice of a concat conv
+    (1, 32, 13, 45, 32, 10, 128, 0),     # 32 x 32 tile, 13 of its 32 columns used, channel slice of a concat conv
     (2, 24, 32, 32, 0, 5, 64, 3),        # 32 x 32 tile (waves split the pixels of 4 x 64 tiles), odd height
     (2, 64, 24, 24, 0, 9, 128, 0),       # 64 x 32 tiles, two x tiles per row, H not a multiple of 4
     (2, 32, 64, 64, 0, 8, 64, 3),        # 32 x 64 tiles
