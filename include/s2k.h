@@ -159,6 +159,49 @@ int s2k_classmap_filter(const void* src, int src_bytes, const int* src_lut, void
                         int size, int mode, unsigned votes, unsigned fixed, int ignore, const unsigned char* labels, const int* index,
                         const int* lut, int nsrc, unsigned long long* hist, unsigned long long* changed, void* stream);
 
+/* Connected components of class maps and the minimum-area sieve (classmap.py; csrc/components.hip).  Two plain functions like
+ * s2k_classmap_filter, not stage kinds: the stage table stays at 55 kinds and S2K_ABI_VERSION at 2.  Each is a fixed, small number of
+ * plain launches on `stream` (three for the labels; one or two for the sieve): no grid-wide barrier, no cooperative launch.
+ *
+ * Definitions (they are the oracle; the reference project has no such operation).  src: [M][H][W] class maps, uint8 (src_bytes == 1) or
+ * int64 (== 8); src_lut: int32[256] or NULL, only with a 1-byte src: the class of a pixel is then src_lut[raw].  A pixel is LABELLED if
+ * its class lies in [0, K), 1 <= K <= 32, and its class bit is not set in `exclude`.  Two labelled pixels are adjacent if they have the
+ * same class and are 4-neighbours (connectivity 4) or 4-neighbours or diagonal neighbours (connectivity 8); components are the connected
+ * classes of that relation.  Maps never see each other, and there is no padding.
+ *   labels  i32 [M][H][W]: the smallest linear index y * W + x over the pixels of the pixel's component (that pixel is the ROOT); -1 for
+ *           an unlabelled pixel.  Canonical: independent of the order in which threads run.
+ *   areas   i32 [M][H][W]: areas[m][i] = pixels of the component whose root is i, 0 where i is no root.  Zeroed by the call.
+ *   counts  u64 [M][K] or NULL: counts[m][k] += components of class k in map m.
+ *   status  u32 [1]: OR-ed into, never cleared.  The parent array keeps parent[i] <= i, so every find / union loop ends within 2 * H * W
+ *           steps by construction; each loop also carries that bound, and a thread that overruns it sets a bit here (1 the tile pass,
+ *           2 the merge across tile edges, 4 the flatten pass, 8 the sieve was handed labels outside [-1, H * W)) and writes nothing
+ *           further.  Non-zero means the outputs are not to be used.
+ * s2k_classmap_components validates every argument on the host before anything is launched: S2K_EFAULT for a NULL src, labels, areas or
+ * status; S2K_EINVAL for src_bytes other than 1 or 8, src_lut with an 8-byte src, K outside 1..32, connectivity other than 4 or 8, bits of
+ * exclude at K or above, M, H or W below 1, H * W >= 2^31 (offsets inside a map are 32-bit; the map offset is 64-bit),
+ * M * ceil(H / 16) * ceil(W / 64) >= 2^24 (one workgroup per 16 x 64 tile of a map).  Messages begin with "classmap_components: ".
+ *
+ * s2k_classmap_sieve, ONE pass: `labels` and `areas` are those of s2k_classmap_components over the same src (with exclude == 0 every
+ * pixel with a class is in a component).  A component is SMALL if its area is below min_area (>= 1) and its class bit is not set in
+ * `fixed`.  With to >= 0 every pixel of a small component becomes `to`.  With to == -1 every small component takes the class of its best
+ * DONOR: a donor is a component that shares at least one pixel EDGE with it (4-neighbour pairs only, whatever the connectivity) and has
+ * a different class; donors are ordered by area >= min_area first, then larger area, then lower root; a small component without a
+ * donor stays as it is.  The class taken is the donor's class in src - all relabelling of a pass is simultaneous.  Unlabelled pixels
+ * are copied unchanged (into a 1-byte dst: their low byte) and donate nothing.  dst: [M][H][W], uint8 or int64 independently of src;
+ * it must not alias src.  best: u64 [M][H][W] workspace for the donor keys, zeroed by the call; NULL is allowed with to >= 0.
+ * changed (u64 [M] or NULL) and hist (u64 [K][K] or NULL, with hist_labels u8 [nsrc][H][W], index i32 [M] and lut i32[256]) are counted
+ * exactly as by s2k_classmap_filter and added to.
+ * Validated on the host before anything is launched: S2K_EFAULT for a NULL src, dst, labels, areas or status; S2K_EINVAL for a width
+ * other than 1 or 8, src_lut with an 8-byte src, src == dst, K outside 1..32, bits of fixed at K or above, min_area < 1, `to` outside
+ * -1..K-1, best NULL with to < 0, M, H or W below 1, H * W >= 2^31, M * ceil(H / 16) * ceil(W / 64) >= 2^24, hist without hist_labels,
+ * index or lut or with nsrc < 1.  Messages begin with "classmap_sieve: ".  Neither function allocates, copies or synchronises. */
+int s2k_classmap_components(const void* src, int src_bytes, const int* src_lut, int M, int H, int W, int K, int connectivity,
+                            unsigned exclude, int* labels, int* areas, unsigned long long* counts, unsigned* status, void* stream);
+int s2k_classmap_sieve(const void* src, int src_bytes, const int* src_lut, void* dst, int dst_bytes, int M, int H, int W, int K,
+                       int min_area, unsigned fixed, int to, const int* labels, const int* areas, unsigned long long* best,
+                       const unsigned char* hist_labels, const int* index, const int* lut, int nsrc, unsigned long long* hist,
+                       unsigned long long* changed, unsigned* status, void* stream);
+
 /* Measured ceilings of the current device for roofline reporting (bench.py): sustained v_mfma_f32_32x32x2_f32 rate with every
  * SIMD issuing back to back (TFLOP/s), the shader clock held meanwhile (MHz), and a float4 stream copy (GB/s, read + write).
  * `scratch`: >= 64 MiB of device memory (size the copy past the caches: 1 GiB+).  Synchronises `stream`.  Not on the hot path. */

@@ -60,6 +60,10 @@ def lib() -> ctypes.CDLL:
     u32 = ctypes.c_uint
     L.s2k_classmap_filter.restype = i32
     L.s2k_classmap_filter.argtypes = [vp, i32, vp, vp, i32] + [i32] * 6 + [u32, u32, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.s2k_classmap_components.restype = i32
+    L.s2k_classmap_components.argtypes = [vp, i32, vp] + [i32] * 5 + [u32, vp, vp, vp, vp, vp]
+    L.s2k_classmap_sieve.restype = i32
+    L.s2k_classmap_sieve.argtypes = [vp, i32, vp, vp, i32] + [i32] * 5 + [u32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     if L.s2k_abi_version() != 2:
         raise S2kError(f"libs2k ABI {L.s2k_abi_version()} != 2")
     if L.s2k_op_size() != D.OP_BYTES or OP_DTYPE.itemsize != D.OP_BYTES:
@@ -174,6 +178,28 @@ def classmap_filter(src, src_lut, dst, dims, size: int, mode: int, votes: int, f
     return lib().s2k_classmap_filter(ptr(src), sb, ptr(src_lut), ptr(dst), db, *[int(d) for d in dims], int(size), int(mode),
                                      int(votes) & 0xffffffff, int(fixed) & 0xffffffff, int(ignore), ptr(labels), ptr(index), ptr(lut),
                                      int(nsrc), ptr(hist), ptr(changed), stream)
+
+
+def classmap_components(src, src_lut, dims, connectivity: int, exclude: int, labels, areas, counts, status, stream: int,
+                        src_bytes: int | None = None) -> int:
+    """s2k_classmap_components (include/s2k.h) as it is: tensors (or None) for the six pointers, dims = (M, H, W, K).  Returns the
+    library's code; the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    sb = (8 if src is None else src.element_size()) if src_bytes is None else int(src_bytes)
+    return lib().s2k_classmap_components(ptr(src), sb, ptr(src_lut), *[int(d) for d in dims], int(connectivity), int(exclude) & 0xffffffff,
+                                         ptr(labels), ptr(areas), ptr(counts), ptr(status), stream)
+
+
+def classmap_sieve(src, src_lut, dst, dims, min_area: int, fixed: int, to: int, labels, areas, best, hist_labels, index, lut, nsrc: int,
+                   hist, changed, status, stream: int, src_bytes: int | None = None, dst_bytes: int | None = None) -> int:
+    """s2k_classmap_sieve (include/s2k.h) as it is: tensors (or None) for the twelve pointers, dims = (M, H, W, K), to = -1 for the
+    donor rule.  Returns the library's code; the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    sb = (8 if src is None else src.element_size()) if src_bytes is None else int(src_bytes)
+    db = (8 if dst is None else dst.element_size()) if dst_bytes is None else int(dst_bytes)
+    return lib().s2k_classmap_sieve(ptr(src), sb, ptr(src_lut), ptr(dst), db, *[int(d) for d in dims], int(min_area), int(fixed) & 0xffffffff,
+                                    int(to), ptr(labels), ptr(areas), ptr(best), ptr(hist_labels), ptr(index), ptr(lut), int(nsrc), ptr(hist),
+                                    ptr(changed), ptr(status), stream)
 
 
 MAE_PANELS = {"original": 0, "masked": 1, "pasted": 2, "reconstruction": 3}      # panel codes of s2k_mae_panels (include/s2k.h)

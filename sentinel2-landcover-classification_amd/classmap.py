@@ -13,6 +13,22 @@ clipped to the image (csrc/classmap.hip; the definition is in include/s2k.h at s
     labels = boundary_to_ignore(labels, num_classes=4, size=3, ignore_index=0)
 
 `TilePredictor.predict / evaluate / render(majority=k)` and `GpuTilePipeline.ignore_label_boundaries` are built on them.
+
+What a window cannot see is the REGIONS of a map.  Every land-cover product removes patches below a minimum mapping unit (the "sieve"),
+after or instead of the majority filter - a 5 x 5 window cannot remove a 30-pixel speck, and it erodes the thin roads a sieve keeps;
+rasterised polygons leave slivers of a few pixels; and the number and size of patches per class is the question after the per-class
+pixel counts of the reference's experiments/label_EDA.py.  All three rest on connected-component labelling, which is block-local
+union-find in LDS, a merge across tile edges and a flatten (csrc/components.hip: three launches whatever the map looks like, where the
+`max_pool2d` propagation idiom needs as many passes as the longest path in a component); the definitions are in include/s2k.h at
+s2k_classmap_components.  Integer work with one exact answer; labels are canonical (a component's smallest linear index).
+
+    labels, areas, counts = connected_components(class_map, 4, connectivity=8, return_areas=True, return_counts=True)
+    clean = sieve(class_map, num_classes=4, min_area=16)                     # small patches take the class of their best neighbour
+    clean, n = sieve(class_map, 4, 16, connectivity=8, iterations=2, fixed=(0,), to=0, return_changed=True)
+
+`TilePredictor.predict / evaluate / render(min_area=a)`, `GpuTilePipeline.ignore_small_label_regions` and `label_components` are built
+on them.  The kernels' loops are bounded by construction and carry that bound; a `status` word the wrappers read once, at the end of a
+public call, reports an overrun as `_lib.S2kError` (it is the only host read they make).
 """
 from __future__ import annotations
 
@@ -25,6 +41,8 @@ MIN_SIZE, MAX_SIZE = 3, 15      # 15 x 15 = 225 votes still fit a byte counter
 STRIP = 64              # columns a wave holds (CLASSMAP_STRIP): STRIP - 2 * (size // 2) of them are outputs
 BAND = 16               # output rows a wave walks (CLASSMAP_BAND)
 MAJORITY, BOUNDARY = _lib.CLASSMAP_MODES["majority"], _lib.CLASSMAP_MODES["boundary"]
+CC_TILE_H, CC_TILE_W = 16, 64   # the tile one workgroup labels in LDS (csrc/components.hip)
+WORKSPACE_BYTES = 512 << 20     # labels + areas + best of one chunk of maps stay below this
 
 
 def strip_outputs(size: int) -> int:
@@ -128,3 +146,152 @@ def boundary_to_ignore(class_map, num_classes: int, size: int = 3, ignore_index:
     dst = torch.empty_like(src)
     launch(src, dst, K, size, BOUNDARY, ignore=ignore_index)
     return dst.view(class_map.shape)
+
+
+# ---- connected components and the minimum-area sieve (csrc/components.hip) ----------------------------------------------------------------
+def check_connectivity(connectivity) -> int:
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int) or connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    return connectivity
+
+
+def check_min_area(min_area) -> int:
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or not 1 <= min_area < 1 << 31:
+        raise ValueError("min_area must be a positive integer (below 2^31)")
+    return min_area
+
+
+def check_to(to, K: int) -> int:
+    """the C entry's `to`: -1 for None (the donor rule), else the class id"""
+    if to is None:
+        return -1
+    if isinstance(to, bool) or not isinstance(to, int) or not 0 <= to < K:
+        raise ValueError(f"to must be None or a class id in [0, {K})")
+    return to
+
+
+def new_status(device) -> torch.Tensor:
+    """the zeroed `status` word of the component kernels (include/s2k.h): OR-ed into by every launch that is handed it"""
+    return torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def raise_status(status: torch.Tensor) -> None:
+    """The one host read of a public call: S2kError if a kernel overran the step bound of its union-find loops (bits 1, 2, 4) or the
+    sieve met labels outside [-1, H * W) (bit 8)."""
+    code = int(status.item())
+    if code:
+        raise _lib.S2kError(f"connected components: status {code:#x} (1 tile pass, 2 edge merge, 4 flatten overran their step bound; "
+                            "8 labels out of range): the outputs are not to be used")
+
+
+def maps_per_chunk(H: int, W: int, bytes_per_pixel: int) -> int:
+    """maps whose workspace of `bytes_per_pixel` stays below WORKSPACE_BYTES (at least one)"""
+    return max(1, (WORKSPACE_BYTES - 1) // (bytes_per_pixel * H * W))
+
+
+def launch_components(src, K: int, connectivity: int, exclude: int, labels, areas, status, counts=None, src_lut=None) -> None:
+    """One s2k_classmap_components call over `src` ([M, H, W], uint8 or int64) on src's device and current stream: three launches."""
+    if not src.is_cuda:
+        raise RuntimeError("connected components run on the GPU (there is no CPU fallback)")
+    M, H, W = src.shape
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.classmap_components(src, src_lut, (M, H, W, K), connectivity, exclude, labels, areas, counts, status,
+                                            torch.cuda.current_stream(src.device).cuda_stream))
+
+
+def launch_sieve(src, dst, K: int, min_area: int, fixed: int, to: int, labels, areas, best, status, src_lut=None, hist_labels=None,
+                 index=None, lut=None, hist=None, changed=None) -> None:
+    """One s2k_classmap_sieve call (one pass) from `src` into `dst` over the labels and areas of `launch_components(src, ...)`."""
+    if not src.is_cuda:
+        raise RuntimeError("the sieve runs on the GPU (there is no CPU fallback)")
+    M, H, W = src.shape
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.classmap_sieve(src, src_lut, dst, (M, H, W, K), min_area, fixed, to, labels, areas, best, hist_labels, index, lut,
+                                       0 if hist_labels is None else hist_labels.shape[0], hist, changed, status,
+                                       torch.cuda.current_stream(src.device).cuda_stream))
+
+
+def run_sieve(src, K: int, min_area: int, connectivity: int, iterations: int, fixed: int, to: int, changed=None, last=None,
+              src_lut=None) -> torch.Tensor:
+    """`iterations` passes of label -> sieve over `src` ([M, H, W]) into a new tensor of src's dtype; the count is fixed, nothing is read
+    between passes.  M is walked in chunks whose workspace (labels, areas and, without `to`, best) stays below WORKSPACE_BYTES.
+    `src_lut` (int32 [256]) reads a uint8 src through a table in the first pass; `last`: the hist operands (labels, index, lut, hist) of
+    the final pass, `index` an int32 [M] device tensor.  `src` is left as it is.  Ends with the status read.  With `src_lut` the
+    result is one byte per pixel: a table value outside [0, 256) is stored as its low byte, and is that byte to every later pass."""
+    M, H, W = src.shape
+    dev = src.device
+    step = maps_per_chunk(H, W, 8 if to >= 0 else 16)
+    n = min(step, M)
+    labels = torch.empty(n, H, W, dtype=torch.int32, device=dev)
+    areas = torch.empty(n, H, W, dtype=torch.int32, device=dev)
+    best = torch.empty(n, H, W, dtype=torch.int64, device=dev) if to < 0 else None
+    ping = [torch.empty(n, H, W, dtype=src.dtype, device=dev) for _ in range(min(iterations - 1, 2))]
+    out = torch.empty_like(src)
+    status = new_status(dev)
+    for m0 in range(0, M, step):
+        m1 = min(m0 + step, M)
+        k = m1 - m0
+        cur, table = src[m0:m1], src_lut
+        for it in range(iterations):
+            final = it == iterations - 1
+            dst = out[m0:m1] if final else ping[it % 2][:k]
+            extra = {}
+            if final and last is not None:
+                extra = dict(hist_labels=last[0], index=last[1][m0:m1], lut=last[2], hist=last[3])
+            launch_components(cur, K, connectivity, 0, labels[:k], areas[:k], status, src_lut=table)
+            launch_sieve(cur, dst, K, min_area, fixed, to, labels[:k], areas[:k], None if best is None else best[:k], status, src_lut=table,
+                         changed=None if changed is None else changed[m0:m1], **extra)
+            cur, table = dst, None
+    raise_status(status)
+    return out
+
+
+@torch.no_grad()
+def connected_components(class_map, num_classes: int, connectivity: int = 4, exclude=(), return_areas: bool = False,
+                         return_counts: bool = False):
+    """int32 labels of `class_map`'s shape (uint8 or int64, [M, H, W] or [H, W], on the GPU): every pixel whose class lies in
+    [0, num_classes) and not in `exclude` gets the smallest linear index y * W + x of its component - same class, joined through 4- or
+    8-neighbours, inside its own map - and every other pixel -1.  return_areas=True adds int32 root areas of the same shape (the pixel
+    count of the component at its root, 0 elsewhere), return_counts=True int64 [M, num_classes]: components per class and map.
+    WORKSPACE_BYTES bounds workspace only: the labels, and the areas when they are asked for, are outputs and are allocated for all
+    M maps at once; areas nobody asked for are workspace and M is walked in chunks."""
+    K, conn = check_classes(num_classes), check_connectivity(connectivity)
+    eb = class_bits(exclude, K, "exclude")
+    src = _check_map(class_map)
+    if not src.is_cuda:
+        raise RuntimeError("connected components run on the GPU (there is no CPU fallback)")
+    M, H, W = src.shape
+    dev = src.device
+    labels = torch.empty(M, H, W, dtype=torch.int32, device=dev)
+    counts = torch.zeros(M, K, dtype=torch.int64, device=dev) if return_counts else None
+    status = new_status(dev)
+    step = M if return_areas else maps_per_chunk(H, W, 4)      # areas nobody asked for are workspace
+    areas = torch.empty(min(step, M), H, W, dtype=torch.int32, device=dev)
+    for m0 in range(0, M, step):
+        m1 = min(m0 + step, M)
+        launch_components(src[m0:m1], K, conn, eb, labels[m0:m1], areas[:m1 - m0], status, None if counts is None else counts[m0:m1])
+    raise_status(status)
+    out = [labels.view(class_map.shape)]
+    if return_areas:
+        out.append(areas.view(class_map.shape))
+    if return_counts:
+        out.append(counts)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+@torch.no_grad()
+def sieve(class_map, num_classes: int, min_area: int, connectivity: int = 4, iterations: int = 1, fixed=(), to=None,
+          return_changed: bool = False):
+    """`class_map` (uint8 or int64, [M, H, W] or [H, W], on the GPU) without its components below `min_area` pixels, `iterations` times:
+    the same dtype and shape.  A small component whose class is not in `fixed` becomes `to`, or without `to` takes the class of its best
+    donor: the components that share a pixel edge with it, those of at least `min_area` first, then the larger area, then the lower
+    root; one without a donor stays.  All relabelling of a pass is simultaneous; pixels outside [0, num_classes) are copied and donate
+    nothing.  return_changed=True adds int64 [M]: the pixels changed, summed over the iterations."""
+    K, area, conn, iterations = check_classes(num_classes), check_min_area(min_area), check_connectivity(connectivity), check_iterations(iterations)
+    fb, t = class_bits(fixed, K, "fixed"), check_to(to, K)
+    src = _check_map(class_map)
+    if not src.is_cuda:
+        raise RuntimeError("the sieve runs on the GPU (there is no CPU fallback)")
+    changed = torch.zeros(src.shape[0], dtype=torch.int64, device=src.device) if return_changed else None
+    out = run_sieve(src, K, area, conn, iterations, fb, t, changed).view(class_map.shape)
+    return (out, changed) if return_changed else out

@@ -92,6 +92,15 @@ int check_classmap_filter(const void*, int, const int*, void*, int, int, int, in
                           const int*, const int*, int, unsigned long long*, unsigned long long*);
 int launch_classmap_filter(const void*, int, const int*, void*, int, int, int, int, int, int, int, unsigned, unsigned, int, const unsigned char*,
                            const int*, const int*, int, unsigned long long*, unsigned long long*, hipStream_t);
+int check_classmap_components(const void*, int, const int*, int, int, int, int, int, unsigned, int*, int*, unsigned long long*, unsigned*);
+int launch_classmap_components(const void*, int, const int*, int, int, int, int, int, unsigned, int*, int*, unsigned long long*, unsigned*,
+                               hipStream_t);
+int check_classmap_sieve(const void*, int, const int*, void*, int, int, int, int, int, int, unsigned, int, const int*, const int*,
+                         unsigned long long*, const unsigned char*, const int*, const int*, int, unsigned long long*, unsigned long long*,
+                         unsigned*);
+int launch_classmap_sieve(const void*, int, const int*, void*, int, int, int, int, int, int, unsigned, int, const int*, const int*,
+                          unsigned long long*, const unsigned char*, const int*, const int*, int, unsigned long long*, unsigned long long*,
+                          unsigned*, hipStream_t);
 
 static int launch_memset(const S2kOp& op, const Ctx& c) {
     const int64_t ref = op.t[S2K_MEMSET_T_DST];
@@ -483,6 +492,37 @@ int s2k_classmap_filter(const void* src, int src_bytes, const int* src_lut, void
     if (rc != S2K_OK) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("classmap_filter: %s", hipGetErrorString(e)); return S2K_EHIP; }
+    return S2K_OK;
+}
+
+int s2k_classmap_components(const void* src, int src_bytes, const int* src_lut, int M, int H, int W, int K, int connectivity,
+                            unsigned exclude, int* labels, int* areas, unsigned long long* counts, unsigned* status, void* stream) {
+    // every argument is validated before the first HIP call (the device guard's included)
+    const int bad = check_classmap_components(src, src_bytes, src_lut, M, H, W, K, connectivity, exclude, labels, areas, counts, status);
+    if (bad != S2K_OK) return bad;
+    DeviceGuard guard(static_cast<hipStream_t>(stream));
+    const int rc = launch_classmap_components(src, src_bytes, src_lut, M, H, W, K, connectivity, exclude, labels, areas, counts, status,
+                                              static_cast<hipStream_t>(stream));
+    if (rc != S2K_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("classmap_components: %s", hipGetErrorString(e)); return S2K_EHIP; }
+    return S2K_OK;
+}
+
+int s2k_classmap_sieve(const void* src, int src_bytes, const int* src_lut, void* dst, int dst_bytes, int M, int H, int W, int K,
+                       int min_area, unsigned fixed, int to, const int* labels, const int* areas, unsigned long long* best,
+                       const unsigned char* hist_labels, const int* index, const int* lut, int nsrc, unsigned long long* hist,
+                       unsigned long long* changed, unsigned* status, void* stream) {
+    // every argument is validated before the first HIP call (the device guard's included)
+    const int bad = check_classmap_sieve(src, src_bytes, src_lut, dst, dst_bytes, M, H, W, K, min_area, fixed, to, labels, areas, best,
+                                         hist_labels, index, lut, nsrc, hist, changed, status);
+    if (bad != S2K_OK) return bad;
+    DeviceGuard guard(static_cast<hipStream_t>(stream));
+    const int rc = launch_classmap_sieve(src, src_bytes, src_lut, dst, dst_bytes, M, H, W, K, min_area, fixed, to, labels, areas, best,
+                                         hist_labels, index, lut, nsrc, hist, changed, status, static_cast<hipStream_t>(stream));
+    if (rc != S2K_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("classmap_sieve: %s", hipGetErrorString(e)); return S2K_EHIP; }
     return S2K_OK;
 }
 

@@ -267,6 +267,48 @@ class GpuTilePipeline:
         self.labels = new
         self.lut = torch.arange(256, dtype=torch.int32).to(self.device)
 
+    @torch.no_grad()
+    def ignore_small_label_regions(self, min_area: int, connectivity: int = 4, ignore_index: int = 0) -> None:
+        """Rewrite the resident labels ONCE so that label regions below `min_area` pixels are ignored: the new labels are
+        `classmap.sieve(lut[labels], num_classes, min_area, connectivity, to=ignore_index, fixed=(ignore_index,))` stored as uint8
+        CLASSES, and the pipeline's label table becomes the identity - exactly what `ignore_label_boundaries` does for the boundary
+        band, with the same consequences for TILE_PREP's `y`, the label statistics and `TilePredictor.evaluate`.  Rasterised polygons
+        leave slivers of a few pixels; with the reference's `masked_loss` convention (class 0 ignored) the default takes them out of
+        loss, metrics and sampling weights.  Both tensors are REPLACED, not written, for the reasons given there.  The label map must
+        map into a byte: a table value outside [0, 256) is stored as its low byte (300 becomes class 44)."""
+        area, conn = CM.check_min_area(min_area), CM.check_connectivity(connectivity)
+        if self.raw is None:
+            raise RuntimeError("call load() first")
+        if self.labels is None:
+            raise ValueError("the pipeline was loaded without labels")
+        if self.label_classes > CM.MAX_CLASSES:
+            raise ValueError(f"the label map has {self.label_classes} classes: regions are labelled for at most {CM.MAX_CLASSES}")
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not 0 <= ignore_index < self.label_classes:
+            raise ValueError(f"ignore_index must be a class id in [0, {self.label_classes})")
+        if not self.labels.is_cuda:
+            raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
+        self.labels = CM.run_sieve(self.labels, self.label_classes, area, conn, 1, 1 << ignore_index, ignore_index, src_lut=self.lut)
+        self.lut = torch.arange(256, dtype=torch.int32).to(self.device)
+
+    @torch.no_grad()
+    def label_components(self, num_classes: int | None = None, indices=None, connectivity: int = 4) -> torch.Tensor:
+        """int64 [M, num_classes] on the device: per selected tile (None = every resident tile), how many connected regions each class
+        (after the label map's remap) forms - the patch count behind the pixel counts of `label_histogram`.  num_classes=None: the
+        label map's own class count.  Remapped labels outside [0, num_classes) belong to no region."""
+        conn = CM.check_connectivity(connectivity)
+        K = CM.check_classes(self.label_classes if num_classes is None else num_classes)
+        idx = self._stats_index(indices, need_labels=True)
+        H, W = self.labels.shape[1:]
+        counts = torch.zeros(idx.numel(), K, dtype=torch.int64, device=self.device)
+        status = CM.new_status(self.device)
+        step = CM.maps_per_chunk(H, W, 9)                       # labels, areas and the gathered label rasters of a chunk
+        for m0 in range(0, idx.numel(), step):
+            src = self.labels.index_select(0, idx[m0:m0 + step].to(self.device))
+            work = torch.empty(2, *src.shape, dtype=torch.int32, device=self.device)
+            CM.launch_components(src, K, conn, 0, work[0], work[1], status, counts[m0:m0 + step], src_lut=self.lut)
+        CM.raise_status(status)
+        return counts
+
     def weighted_indices(self, weights, num_samples: int, generator: torch.Generator | None = None) -> torch.Tensor:
         """int64 [num_samples] positions drawn with replacement in proportion to `weights`, on the host: exactly what
         `WeightedRandomSampler(weights, num_samples, True, generator=generator)` yields.  They index the tiles the weights were

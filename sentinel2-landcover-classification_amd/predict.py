@@ -12,6 +12,7 @@ a gather with a fixed summation order, so a prediction is bit-identical from run
     predictor.evaluate(metrics)                                         # whole-tile confusion counts into metrics.hist
     metrics.compute()                                                   # whole-tile IoU / accuracy / F1
     class_map = predictor.predict([3, 17], majority=5)                  # after the 5 x 5 majority filter (classmap.py); so evaluate, render
+    class_map = predictor.predict([3, 17], majority=5, min_area=16)     # then without its patches below 16 pixels (classmap.sieve)
 """
 from __future__ import annotations
 
@@ -104,29 +105,37 @@ class TilePredictor:
         self.profile = window_profile(self.S, window)
 
     # ---- public surface ------------------------------------------------------------------------------------------------------
-    def predict(self, indices=None, majority: int | None = None, iterations: int = 1) -> torch.Tensor:
+    def predict(self, indices=None, majority: int | None = None, iterations: int = 1, min_area: int | None = None,
+                connectivity: int = 4) -> torch.Tensor:
         """int64 [M, H, W] on the device: the class of every pixel of the selected tiles (None = every resident tile).  majority=k:
-        after `iterations` passes of the k x k majority filter (`classmap.majority_filter`: every class votes, none is fixed)."""
-        if majority is None:
-            return self._run(indices, want="mask")
-        size, its = CM.check_size(majority), CM.check_iterations(iterations)
-        return CM.run_majority(self._run(indices, want="mask"), self.K, size, its, CM.class_bits(None, self.K, "votes"), 0)
+        after `iterations` passes of the k x k majority filter (`classmap.majority_filter`: every class votes, none is fixed).
+        min_area=a: after one pass of the minimum-area sieve (`classmap.sieve(map, K, a, connectivity)`: the donor rule, no class
+        fixed), which runs after the majority filter when both are given."""
+        size, its, area, conn = self._post(majority, iterations, min_area, connectivity)
+        out = self._run(indices, want="mask")
+        if size is not None:
+            out = CM.run_majority(out, self.K, size, its, CM.class_bits(None, self.K, "votes"), 0)
+        if area is not None:
+            out = CM.run_sieve(out, self.K, area, conn, 1, 0, -1)
+        return out
 
     def predict_blend(self, indices=None) -> torch.Tensor:
         """float32 [M, K, H, W] on the device: the blended probabilities (blend="probs") or logits."""
         return self._run(indices, want="blend")
 
-    def evaluate(self, metrics, indices=None, majority: int | None = None, iterations: int = 1) -> None:
+    def evaluate(self, metrics, indices=None, majority: int | None = None, iterations: int = 1, min_area: int | None = None,
+                 connectivity: int = 4) -> None:
         """Add the whole-tile confusion counts of the selected tiles - hist[true][predicted] against the pipeline's resident labels
         after its label map - into `metrics.hist` (a `metrics.SegMetrics`), inside the blending launch itself.  majority=k: the counts
         of the map after `iterations` passes of the k x k majority filter, added by the last filter launch (no separate CONFUSION
-        pass, no int64 label tensor)."""
+        pass, no int64 label tensor).  min_area=a: the counts of the map after the sieve (after the majority filter, if given), added
+        by the sieve's relabel launch in the same way."""
         if int(metrics.C) != self.K:
             raise ValueError("metrics.num_classes differs from the predictor's")
-        if majority is None:
+        size, its, area, conn = self._post(majority, iterations, min_area, connectivity)
+        if size is None and area is None:
             self._run(indices, want="hist", metrics=metrics)
             return
-        size, its = CM.check_size(majority), CM.check_iterations(iterations)
         pipe = self.pipe
         if pipe.raw is None:
             raise RuntimeError("call load() first")
@@ -134,24 +143,36 @@ class TilePredictor:
         mask = self._run(idx, want="mask")
         if metrics.hist.device != pipe.device:
             metrics.hist = metrics.hist.to(pipe.device)
-        CM.run_majority(mask, self.K, size, its, CM.class_bits(None, self.K, "votes"), 0,
-                        last=(pipe.labels, idx.to(pipe.device), pipe.lut, metrics.hist))
+        last = (pipe.labels, idx.to(pipe.device), pipe.lut, metrics.hist)
+        if size is not None:
+            mask = CM.run_majority(mask, self.K, size, its, CM.class_bits(None, self.K, "votes"), 0, last=None if area is not None else last)
+        if area is not None:
+            CM.run_sieve(mask, self.K, area, conn, 1, 0, -1, last=last)
 
-    def render(self, indices, palette, alpha: float = 0.5, majority: int | None = None, iterations: int = 1) -> torch.Tensor:
+    def render(self, indices, palette, alpha: float = 0.5, majority: int | None = None, iterations: int = 1, min_area: int | None = None,
+               connectivity: int = 4) -> torch.Tensor:
         """uint8 [M, H, W, 3] on the device: the whole-tile quicklook of the selected tiles (`GpuTilePipeline.quicklook`, its default
-        bands and percentile) with the predicted class map (`predict(indices, majority, iterations)`) laid over it in the colours of
-        `palette` (uint8 [>= num_classes, 3]) at opacity `alpha` (`render.overlay`)."""
-        if majority is not None:
-            CM.check_size(majority)
-            CM.check_iterations(iterations)
+        bands and percentile) with the predicted class map (`predict(indices, majority, iterations, min_area, connectivity)`) laid
+        over it in the colours of `palette` (uint8 [>= num_classes, 3]) at opacity `alpha` (`render.overlay`)."""
+        self._post(majority, iterations, min_area, connectivity)
         pal = QL.check_palette(palette)
         QL.alpha_code(alpha)
         if pal.shape[0] < self.K:
             raise ValueError("palette needs one colour per class")
         picture = self.pipe.quicklook(indices, whole_tile=True)          # ValueError first, then the refusal to run off the GPU
-        return overlay(picture, self.predict(indices, majority, iterations), pal, alpha)
+        return overlay(picture, self.predict(indices, majority, iterations, min_area, connectivity), pal, alpha)
 
     # ---- implementation ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _post(majority, iterations, min_area, connectivity):
+        """(size, iterations, min_area, connectivity) of the map filters, validated; size / min_area None where not asked for"""
+        size = its = area = conn = None
+        if majority is not None:
+            size, its = CM.check_size(majority), CM.check_iterations(iterations)
+        if min_area is not None:
+            area, conn = CM.check_min_area(min_area), CM.check_connectivity(connectivity)
+        return size, its, area, conn
+
     def _geometry(self):
         H, W = (int(v) for v in self.pipe.raw.shape[2:])
         ys, xs = window_origins(H, self.S, self.stride), window_origins(W, self.S, self.stride)
