@@ -202,6 +202,43 @@ int s2k_classmap_sieve(const void* src, int src_bytes, const int* src_lut, void*
                        const unsigned char* hist_labels, const int* index, const int* lut, int nsrc, unsigned long long* hist,
                        unsigned long long* changed, unsigned* status, void* stream);
 
+/* Exact Euclidean distance transform of class maps, the nearest site and distance-binned confusion counts (classmap.py;
+ * csrc/distance.hip).  A plain function like s2k_classmap_components, not a stage kind: the stage table stays at 55 kinds and
+ * S2K_ABI_VERSION at 2.  Two plain launches on `stream` whatever the map looks like (a column pass into `work`, a row pass): no
+ * grid-wide barrier, no cooperative launch.
+ *
+ * Definitions (they are the oracle; the reference project has no such operation).  src: [M][H][W] class maps, uint8 (src_bytes == 1) or
+ * int64 (== 8); src_lut: int32[256] or NULL, only with a 1-byte src: the class of a pixel is then src_lut[raw].  1 <= K <= 32.  A pixel
+ * is LABELLED if its class lies in [0, K) and its class bit is not set in `exclude`.  A pixel is a SITE
+ *   mode 0 (classes)   if it is labelled and its class bit is set in `sites` (non-zero, inside [0, K), disjoint from exclude);
+ *   mode 1 (boundary)  if it is labelled and at least one neighbour is labelled with a DIFFERENT class: the 4-neighbours at
+ *                      connectivity 4, those and the diagonals at 8, only neighbours inside the map.  Unlabelled pixels are never
+ *                      sites and never make a neighbour a site; both sides of a boundary are sites.  `sites` must be 0.
+ *   dist2    i32 [M][H][W]: for EVERY pixel, labelled or not, the minimum over the sites s of its own map of (y - ys)^2 + (x - xs)^2;
+ *            0 at a site; 2^31 - 1 (NO_SITE) where the map has no site.  Maps never see each other.
+ *   nearest  i32 [M][H][W] or NULL: the linear index ys * W + xs of a nearest site, -1 where there is none.  The tie rule is canonical
+ *            and part of the contract: among the sites at distance dist2, the one with the smallest linear index.
+ *   work     M * H * W 16-bit column offsets (s2k_classmap_distance_workspace(M, H, W) bytes), written and read by the call.
+ *   hist     u64 [n_edges + 1][K][K] or NULL, ADDED to by the launch that writes dist2 (without it that launch does no counting work):
+ *            with other ([M][H][W], uint8 or int64: other_bytes; no table) and edges (i32 [n_edges] in HOST memory, 1 <= n_edges <= 8,
+ *            each >= 0, strictly ascending: thresholds on dist2), for every pixel whose src class and whose `other` class both lie in
+ *            [0, K): hist[b][src class][other class] += 1, b = the number of j with dist2 > edges[j].  This count ignores `exclude`
+ *            (the CONFUSION convention); NO_SITE lands in the last bin.  Integer sums: exact.
+ * Limits, all checked on the host before anything is launched: H, W <= 16384 (an offset then fits 16 bits and dist2 31 bits);
+ * H * W < 2^31 (offsets inside a map are 32-bit; the map offset is 64-bit); M * ceil(W / 64) < 2^24 (one 64-thread workgroup per 64
+ * columns of a map) and M * ceil(H / R) < 2^24 with R = min(8, 65535 / W) (one workgroup per R rows of a map: it counts its pixels in
+ * 16-bit bins).  S2K_EFAULT for a NULL src, dist2 or work; S2K_EINVAL for src_bytes (or, with hist, other_bytes) other than 1 or 8,
+ * src_lut with an 8-byte src, K outside 1..32, mode other than 0 or 1, connectivity other than 4 or 8, bits of sites or exclude at K or
+ * above, mode 0 with sites == 0 or sites overlapping exclude, mode 1 with sites != 0, hist without other or edges, n_edges outside
+ * 1..8, an edge below 0 or not above its predecessor, M, H or W below 1, a limit exceeded.  Messages begin with "classmap_distance: ".
+ * Every loop of the kernels is bounded by construction and carries that bound as its trip limit (the column sweeps H, the search W):
+ * there is no data-dependent loop and therefore no status word.  The function does no allocation, no copy and no synchronisation.
+ * s2k_classmap_distance_workspace: bytes of `work` (0 for M, H or W below 1). */
+int s2k_classmap_distance(const void* src, int src_bytes, const int* src_lut, int M, int H, int W, int K, int mode, unsigned sites,
+                          int connectivity, unsigned exclude, void* work, int* dist2, int* nearest, const void* other, int other_bytes,
+                          const int* edges, int n_edges, unsigned long long* hist, void* stream);
+size_t s2k_classmap_distance_workspace(int M, int H, int W);
+
 /* Measured ceilings of the current device for roofline reporting (bench.py): sustained v_mfma_f32_32x32x2_f32 rate with every
  * SIMD issuing back to back (TFLOP/s), the shader clock held meanwhile (MHz), and a float4 stream copy (GB/s, read + write).
  * `scratch`: >= 64 MiB of device memory (size the copy past the caches: 1 GiB+).  Synchronises `stream`.  Not on the hot path. */

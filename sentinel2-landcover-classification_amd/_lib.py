@@ -64,6 +64,10 @@ def lib() -> ctypes.CDLL:
     L.s2k_classmap_components.argtypes = [vp, i32, vp] + [i32] * 5 + [u32, vp, vp, vp, vp, vp]
     L.s2k_classmap_sieve.restype = i32
     L.s2k_classmap_sieve.argtypes = [vp, i32, vp, vp, i32] + [i32] * 5 + [u32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.s2k_classmap_distance.restype = i32
+    L.s2k_classmap_distance.argtypes = [vp, i32, vp] + [i32] * 5 + [u32, i32, u32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
+    L.s2k_classmap_distance_workspace.restype = ctypes.c_size_t
+    L.s2k_classmap_distance_workspace.argtypes = [i32] * 3
     if L.s2k_abi_version() != 2:
         raise S2kError(f"libs2k ABI {L.s2k_abi_version()} != 2")
     if L.s2k_op_size() != D.OP_BYTES or OP_DTYPE.itemsize != D.OP_BYTES:
@@ -200,6 +204,28 @@ def classmap_sieve(src, src_lut, dst, dims, min_area: int, fixed: int, to: int, 
     return lib().s2k_classmap_sieve(ptr(src), sb, ptr(src_lut), ptr(dst), db, *[int(d) for d in dims], int(min_area), int(fixed) & 0xffffffff,
                                     int(to), ptr(labels), ptr(areas), ptr(best), ptr(hist_labels), ptr(index), ptr(lut), int(nsrc), ptr(hist),
                                     ptr(changed), ptr(status), stream)
+
+
+CLASSMAP_DISTANCE_MODES = {"classes": 0, "boundary": 1}      # site modes of s2k_classmap_distance (include/s2k.h)
+
+
+def classmap_distance(src, src_lut, dims, mode: int, sites: int, connectivity: int, exclude: int, work, dist2, nearest, other, edges, hist,
+                      stream: int, src_bytes: int | None = None, other_bytes: int | None = None, n_edges: int | None = None) -> int:
+    """s2k_classmap_distance (include/s2k.h) as it is: tensors (or None) for the seven pointers, dims = (M, H, W, K), `edges` a sequence
+    of ints (host memory) or None.  Returns the library's code; the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    sb = (8 if src is None else src.element_size()) if src_bytes is None else int(src_bytes)
+    ob = (8 if other is None else other.element_size()) if other_bytes is None else int(other_bytes)
+    ne = (0 if edges is None else len(edges)) if n_edges is None else int(n_edges)
+    arr = None if edges is None else (ctypes.c_int * max(len(edges), 1))(*[int(e) for e in edges])
+    return lib().s2k_classmap_distance(ptr(src), sb, ptr(src_lut), *[int(d) for d in dims], int(mode), int(sites) & 0xffffffff,
+                                       int(connectivity), int(exclude) & 0xffffffff, ptr(work), ptr(dist2), ptr(nearest), ptr(other), ob,
+                                       arr, ne, ptr(hist), stream)
+
+
+def classmap_distance_workspace(M: int, H: int, W: int) -> int:
+    """bytes of the `work` buffer of s2k_classmap_distance for M maps of H x W"""
+    return int(lib().s2k_classmap_distance_workspace(int(M), int(H), int(W)))
 
 
 MAE_PANELS = {"original": 0, "masked": 1, "pasted": 2, "reconstruction": 3}      # panel codes of s2k_mae_panels (include/s2k.h)

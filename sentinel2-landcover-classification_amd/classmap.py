@@ -29,8 +29,26 @@ s2k_classmap_components.  Integer work with one exact answer; labels are canonic
 `TilePredictor.predict / evaluate / render(min_area=a)`, `GpuTilePipeline.ignore_small_label_regions` and `label_components` are built
 on them.  The kernels' loops are bounded by construction and carry that bound; a `status` word the wrappers read once, at the end of a
 public call, reports an overrun as `_lib.S2kError` (it is the only host read they make).
+
+What neither a window nor a region gives is a DISTANCE: how far a pixel is from the nearest class boundary, or from the nearest pixel of
+some classes.  It is the quantity behind the band itself (`boundary_to_ignore` can only draw a square window of 3 to 15 pixels),
+behind the question whether a model's errors sit at the label boundaries (`metrics.DistanceBinnedMetrics`: confusion counts binned by
+the distance to the nearest boundary), and behind filling no-data from the nearest labelled pixel.  All rest on the exact Euclidean
+distance transform (csrc/distance.hip: a column pass and a row pass, two launches whatever the map looks like; the definitions are in
+include/s2k.h at s2k_classmap_distance).  Integer work with one exact answer: squared distances, and the nearest site with a canonical
+tie rule (the smallest linear index).  Every loop of the kernels is bounded by its trip limit; there is no status word to read.
+
+    d2 = distance_transform(class_map, 4)                                    # int32 squared distance to the nearest class boundary
+    d2, site = distance_transform(class_map, 4, to=(2, 3), return_nearest=True)      # ... to the nearest pixel of class 2 or 3
+    labels = boundary_band(labels, num_classes=4, distance=2.5, ignore_index=0)      # the Euclidean sibling of boundary_to_ignore
+    filled = fill_nearest(class_map, 4, fill=(0,))                           # class 0 and no-data take their nearest other pixel's class
+
+`GpuTilePipeline.ignore_label_boundaries_within`, `metrics.DistanceBinnedMetrics` and `TilePredictor.evaluate_by_distance` are built on
+them.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -43,6 +61,10 @@ BAND = 16               # output rows a wave walks (CLASSMAP_BAND)
 MAJORITY, BOUNDARY = _lib.CLASSMAP_MODES["majority"], _lib.CLASSMAP_MODES["boundary"]
 CC_TILE_H, CC_TILE_W = 16, 64   # the tile one workgroup labels in LDS (csrc/components.hip)
 WORKSPACE_BYTES = 512 << 20     # labels + areas + best of one chunk of maps stay below this
+NO_SITE = 2**31 - 1             # dist2 where a map has no site (nearest is -1 there)
+EDT_COLS, EDT_ROWS = 64, 8      # columns of a column-pass workgroup; rows a row-pass workgroup walks (csrc/distance.hip)
+EDT_MAX_EDGES, EDT_MAX_DIM = 8, 16384
+TO_CLASSES, TO_BOUNDARY = _lib.CLASSMAP_DISTANCE_MODES["classes"], _lib.CLASSMAP_DISTANCE_MODES["boundary"]
 
 
 def strip_outputs(size: int) -> int:
@@ -295,3 +317,181 @@ def sieve(class_map, num_classes: int, min_area: int, connectivity: int = 4, ite
     changed = torch.zeros(src.shape[0], dtype=torch.int64, device=src.device) if return_changed else None
     out = run_sieve(src, K, area, conn, iterations, fb, t, changed).view(class_map.shape)
     return (out, changed) if return_changed else out
+
+
+# ---- the exact Euclidean distance transform (csrc/distance.hip) ----------------------------------------------------------------------------
+def check_ignore_index(ignore_index, K: int) -> int:
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not 0 <= ignore_index < K:
+        raise ValueError(f"ignore_index must be a class id in [0, {K})")
+    return ignore_index
+
+
+def squared_threshold(distance, what: str = "distance") -> int:
+    """floor(distance^2) of a distance in pixels (finite, >= 0): the threshold on dist2 that `dist2 <= t` is `d <= distance` for"""
+    if isinstance(distance, bool) or not isinstance(distance, (int, float)) or not math.isfinite(distance) or distance < 0:
+        raise ValueError(f"{what} must be a finite number of pixels >= 0")
+    return min(math.floor(distance * distance), NO_SITE - 1)
+
+
+def check_edges(edges) -> list:
+    """the thresholds on dist2 of 1..EDT_MAX_EDGES bin edges in pixels: floor(edge^2), strictly ascending"""
+    try:
+        edges = list(edges)
+    except TypeError:
+        raise ValueError("edges must be a sequence of distances in pixels") from None
+    if not 1 <= len(edges) <= EDT_MAX_EDGES:
+        raise ValueError(f"edges must hold 1..{EDT_MAX_EDGES} distances")
+    out = [squared_threshold(e, "an edge") for e in edges]
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"edges must ascend strictly after floor(edge^2): got {out}")
+    return out
+
+
+def check_sites(to, K: int, exclude: int):
+    """(mode, sites) of the C entry for `to`: "boundary", or an iterable of class ids that `exclude` does not name"""
+    if isinstance(to, str):
+        if to != "boundary":
+            raise ValueError('to must be "boundary" or an iterable of class ids')
+        return TO_BOUNDARY, 0
+    try:
+        ids = list(to)
+    except TypeError:
+        raise ValueError('to must be "boundary" or an iterable of class ids') from None
+    sites = class_bits(ids, K, "to")
+    if sites == 0:
+        raise ValueError("to must name at least one class")
+    if sites & exclude:
+        raise ValueError("to and exclude overlap")
+    return TO_CLASSES, sites
+
+
+def _check_dims(src) -> None:
+    if src.shape[1] > EDT_MAX_DIM or src.shape[2] > EDT_MAX_DIM:
+        raise ValueError(f"the distance transform takes maps of at most {EDT_MAX_DIM} x {EDT_MAX_DIM}")
+
+
+def launch_distance(src, K: int, mode: int, sites: int, connectivity: int, exclude: int, work, dist2, nearest=None, src_lut=None, other=None,
+                    edges=None, hist=None) -> None:
+    """One s2k_classmap_distance call over `src` ([M, H, W], uint8 or int64) on src's device and current stream: two launches."""
+    if not src.is_cuda:
+        raise RuntimeError("the distance transform runs on the GPU (there is no CPU fallback)")
+    M, H, W = src.shape
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.classmap_distance(src, src_lut, (M, H, W, K), mode, sites, connectivity, exclude, work, dist2, nearest, other, edges,
+                                          hist, torch.cuda.current_stream(src.device).cuda_stream))
+
+
+def run_distance(src, K: int, mode: int, sites: int, connectivity: int, exclude: int, want_nearest: bool = False, src_lut=None):
+    """(dist2, nearest or None), int32 [M, H, W], of `src` ([M, H, W]); M is walked in chunks whose workspace (the 16-bit column offsets)
+    stays below WORKSPACE_BYTES.  The outputs are allocated for all M maps at once."""
+    M, H, W = src.shape
+    dev = src.device
+    step = maps_per_chunk(H, W, 2)
+    work = torch.empty(min(step, M), H, W, dtype=torch.int16, device=dev)
+    dist2 = torch.empty(M, H, W, dtype=torch.int32, device=dev)
+    nearest = torch.empty(M, H, W, dtype=torch.int32, device=dev) if want_nearest else None
+    for m0 in range(0, M, step):
+        m1 = min(m0 + step, M)
+        launch_distance(src[m0:m1], K, mode, sites, connectivity, exclude, work[:m1 - m0], dist2[m0:m1],
+                        None if nearest is None else nearest[m0:m1], src_lut=src_lut)
+    return dist2, nearest
+
+
+def count_by_distance(src, other, K: int, connectivity: int, exclude: int, edges, hist, src_lut=None) -> None:
+    """Add the confusion counts hist[bin][src class][other class] of `src` against `other` ([M, H, W] each), binned by the squared
+    distance to the nearest class boundary of `src` (mode 1) at the thresholds `edges`, into `hist` (int64 [len(edges) + 1, K, K]) -
+    from the launch that computes the distances.  Here dist2 is workspace too: M is walked in chunks of 6 bytes a pixel."""
+    M, H, W = src.shape
+    dev = src.device
+    step = maps_per_chunk(H, W, 6)
+    n = min(step, M)
+    work = torch.empty(n, H, W, dtype=torch.int16, device=dev)
+    dist2 = torch.empty(n, H, W, dtype=torch.int32, device=dev)
+    for m0 in range(0, M, step):
+        m1 = min(m0 + step, M)
+        launch_distance(src[m0:m1], K, TO_BOUNDARY, 0, connectivity, exclude, work[:m1 - m0], dist2[:m1 - m0], src_lut=src_lut,
+                        other=other[m0:m1], edges=edges, hist=hist)
+
+
+def run_band(src, K: int, threshold: int, connectivity: int, ignore_index: int, src_lut=None) -> torch.Tensor:
+    """`src` ([M, H, W]) with every labelled pixel other than class `ignore_index` whose dist2 to the nearest class boundary (mode 1,
+    `ignore_index` excluded) is at most `threshold` set to `ignore_index`.  With `src_lut` (int32 [256]) the classes are src_lut[src]
+    and the result is stored as uint8 classes.  The band itself is a torch expression over dist2, chunk by chunk."""
+    M, H, W = src.shape
+    dev = src.device
+    step = maps_per_chunk(H, W, 6 + (8 if src_lut is not None else 0))
+    n = min(step, M)
+    work = torch.empty(n, H, W, dtype=torch.int16, device=dev)
+    dist2 = torch.empty(n, H, W, dtype=torch.int32, device=dev)
+    out = torch.empty_like(src)
+    for m0 in range(0, M, step):
+        m1 = min(m0 + step, M)
+        part = src[m0:m1]
+        launch_distance(part, K, TO_BOUNDARY, 0, connectivity, 1 << ignore_index, work[:m1 - m0], dist2[:m1 - m0], src_lut=src_lut)
+        cls = part if src_lut is None else src_lut[part.long()]
+        mark = (cls >= 0) & (cls < K) & (cls != ignore_index) & (dist2[:m1 - m0] <= threshold)
+        out[m0:m1] = torch.where(mark, torch.full_like(cls, ignore_index), cls).to(src.dtype)
+    return out
+
+
+@torch.no_grad()
+def distance_transform(class_map, num_classes: int, to="boundary", connectivity: int = 4, exclude=(), return_nearest: bool = False):
+    """int32 SQUARED Euclidean distances of `class_map`'s shape (uint8 or int64, [M, H, W] or [H, W], on the GPU): for every pixel the
+    squared distance to the nearest SITE of its own map, 0 at a site, NO_SITE where the map has none.  A pixel is labelled if its class
+    lies in [0, num_classes) and not in `exclude`.  to="boundary": the sites are the labelled pixels with a labelled 4- or 8-neighbour
+    of a different class (both sides of a boundary; unlabelled pixels make no boundary).  to=(ids): the labelled pixels of those classes.
+    return_nearest=True adds the int32 linear index y * W + x of the nearest site (-1 where there is none); among equally near sites it
+    is the one with the smallest index."""
+    K, conn = check_classes(num_classes), check_connectivity(connectivity)
+    eb = class_bits(exclude, K, "exclude")
+    mode, sites = check_sites(to, K, eb)
+    src = _check_map(class_map)
+    _check_dims(src)
+    if not src.is_cuda:
+        raise RuntimeError("the distance transform runs on the GPU (there is no CPU fallback)")
+    dist2, nearest = run_distance(src, K, mode, sites, conn, eb, bool(return_nearest))
+    dist2 = dist2.view(class_map.shape)
+    return (dist2, nearest.view(class_map.shape)) if return_nearest else dist2
+
+
+@torch.no_grad()
+def boundary_band(class_map, num_classes: int, distance, connectivity: int = 4, ignore_index: int = 0) -> torch.Tensor:
+    """`class_map` with every labelled pixel within `distance` pixels (Euclidean: dist2 <= floor(distance^2)) of a class boundary set to
+    `ignore_index`: the Euclidean sibling of `boundary_to_ignore`.  The boundaries are those of `distance_transform(...,
+    to="boundary", exclude=(ignore_index,))`: a pixel that only touches the ignored class or a pixel outside [0, num_classes) is no
+    boundary, so the ignored region does not grow on its own.  distance = 0 marks the boundary pixels themselves.  Same dtype and
+    shape."""
+    K, conn = check_classes(num_classes), check_connectivity(connectivity)
+    threshold = squared_threshold(distance)
+    ignore = check_ignore_index(ignore_index, K)
+    src = _check_map(class_map)
+    _check_dims(src)
+    if not src.is_cuda:
+        raise RuntimeError("the distance transform runs on the GPU (there is no CPU fallback)")
+    return run_band(src, K, threshold, conn, ignore).view(class_map.shape)
+
+
+@torch.no_grad()
+def fill_nearest(class_map, num_classes: int, fill) -> torch.Tensor:
+    """`class_map` with every pixel that lies outside [0, num_classes), or whose class is in `fill`, replaced by the class of its nearest
+    pixel that is neither (of the smallest linear index among equally near ones, so the result is exact).  A map without such a pixel is
+    returned unchanged.  `fill` must leave at least one class.  Same dtype and shape."""
+    K = check_classes(num_classes)
+    fb = class_bits(fill, K, "fill")
+    sites = ((1 << K) - 1) & ~fb
+    if sites == 0:
+        raise ValueError("fill must leave at least one class to fill from")
+    src = _check_map(class_map)
+    _check_dims(src)
+    if not src.is_cuda:
+        raise RuntimeError("the distance transform runs on the GPU (there is no CPU fallback)")
+    M, H, W = src.shape
+    _, nearest = run_distance(src, K, TO_CLASSES, sites, 4, 0, True)
+    flat = src.view(M, H * W)
+    holes = (flat < 0) | (flat >= K) if src.dtype == torch.int64 else flat >= K
+    for c in range(K):
+        if (fb >> c) & 1:
+            holes |= flat == c
+    near = nearest.view(M, H * W).long()
+    taken = torch.gather(flat, 1, near.clamp(min=0))
+    return torch.where(holes & (near >= 0), taken, flat).view(class_map.shape)

@@ -101,6 +101,11 @@ int check_classmap_sieve(const void*, int, const int*, void*, int, int, int, int
 int launch_classmap_sieve(const void*, int, const int*, void*, int, int, int, int, int, int, unsigned, int, const int*, const int*,
                           unsigned long long*, const unsigned char*, const int*, const int*, int, unsigned long long*, unsigned long long*,
                           unsigned*, hipStream_t);
+int check_classmap_distance(const void*, int, const int*, int, int, int, int, int, unsigned, int, unsigned, void*, int*, int*, const void*, int,
+                            const int*, int, unsigned long long*);
+int launch_classmap_distance(const void*, int, const int*, int, int, int, int, int, unsigned, int, unsigned, void*, int*, int*, const void*, int,
+                             const int*, int, unsigned long long*, hipStream_t);
+size_t classmap_distance_workspace(int, int, int);
 
 static int launch_memset(const S2kOp& op, const Ctx& c) {
     const int64_t ref = op.t[S2K_MEMSET_T_DST];
@@ -525,6 +530,24 @@ int s2k_classmap_sieve(const void* src, int src_bytes, const int* src_lut, void*
     if (e != hipSuccess) { set_error("classmap_sieve: %s", hipGetErrorString(e)); return S2K_EHIP; }
     return S2K_OK;
 }
+
+int s2k_classmap_distance(const void* src, int src_bytes, const int* src_lut, int M, int H, int W, int K, int mode, unsigned sites,
+                          int connectivity, unsigned exclude, void* work, int* dist2, int* nearest, const void* other, int other_bytes,
+                          const int* edges, int n_edges, unsigned long long* hist, void* stream) {
+    // every argument is validated before the first HIP call (the device guard's included)
+    const int bad = check_classmap_distance(src, src_bytes, src_lut, M, H, W, K, mode, sites, connectivity, exclude, work, dist2, nearest, other,
+                                            other_bytes, edges, n_edges, hist);
+    if (bad != S2K_OK) return bad;
+    DeviceGuard guard(static_cast<hipStream_t>(stream));
+    const int rc = launch_classmap_distance(src, src_bytes, src_lut, M, H, W, K, mode, sites, connectivity, exclude, work, dist2, nearest, other,
+                                            other_bytes, edges, n_edges, hist, static_cast<hipStream_t>(stream));
+    if (rc != S2K_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("classmap_distance: %s", hipGetErrorString(e)); return S2K_EHIP; }
+    return S2K_OK;
+}
+
+size_t s2k_classmap_distance_workspace(int M, int H, int W) { return classmap_distance_workspace(M, H, W); }
 
 int s2k_selftest_mfma(const float* a, const float* b, float* d, void* stream) {
     if (!a || !b || !d) { set_error("selftest: null pointer"); return S2K_EINVAL; }

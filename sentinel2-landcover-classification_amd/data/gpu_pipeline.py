@@ -268,6 +268,28 @@ class GpuTilePipeline:
         self.lut = torch.arange(256, dtype=torch.int32).to(self.device)
 
     @torch.no_grad()
+    def ignore_label_boundaries_within(self, distance, connectivity: int = 4, ignore_index: int = 0) -> None:
+        """Rewrite the resident labels ONCE so that every labelled pixel within `distance` pixels (Euclidean) of a class boundary is
+        ignored: the new labels are `classmap.boundary_band(lut[labels], num_classes, distance, connectivity, ignore_index)` stored as
+        uint8 CLASSES, and the pipeline's label table becomes the identity - exactly what `ignore_label_boundaries` does for its
+        square window, with the same consequences for TILE_PREP's `y`, the label statistics and `TilePredictor.evaluate`, and the same
+        replace-not-write rule for both tensors.  distance = 0 marks the boundary pixels themselves; `DistanceBinnedMetrics` says how
+        wide the band should be.  The label map must map into a byte: a table value outside [0, 256) is stored as its low byte."""
+        conn, threshold = CM.check_connectivity(connectivity), CM.squared_threshold(distance)
+        if self.raw is None:
+            raise RuntimeError("call load() first")
+        if self.labels is None:
+            raise ValueError("the pipeline was loaded without labels")
+        if self.label_classes > CM.MAX_CLASSES:
+            raise ValueError(f"the label map has {self.label_classes} classes: boundaries are marked for at most {CM.MAX_CLASSES}")
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not 0 <= ignore_index < self.label_classes:
+            raise ValueError(f"ignore_index must be a class id in [0, {self.label_classes})")
+        if not self.labels.is_cuda:
+            raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
+        self.labels = CM.run_band(self.labels, self.label_classes, threshold, conn, ignore_index, src_lut=self.lut)
+        self.lut = torch.arange(256, dtype=torch.int32).to(self.device)
+
+    @torch.no_grad()
     def ignore_small_label_regions(self, min_area: int, connectivity: int = 4, ignore_index: int = 0) -> None:
         """Rewrite the resident labels ONCE so that label regions below `min_area` pixels are ignored: the new labels are
         `classmap.sieve(lut[labels], num_classes, min_area, connectivity, to=ignore_index, fixed=(ignore_index,))` stored as uint8

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import torch
 
+from . import classmap as CM
 from .stage_call import StageCall, cached
 
 _CALLS = {}      # the packed CONFUSION calls of this process (stage_call.cached)
@@ -78,3 +79,60 @@ def metrics_from_hist(h: torch.Tensor, ignore_index: int | None) -> dict:
         acc = tp.sum() / n if n > 0 else torch.tensor(0.0, dtype=torch.float64)
         f1 = acc
     return {"confusion_matrix": cmn.float(), "iou": iou.float(), "accuracy": acc.float(), "f1": f1.float()}
+
+
+class DistanceBinnedMetrics:
+    """Confusion counts binned by the distance of a pixel to the nearest class boundary of the LABELS: do the errors sit where two
+    classes meet (where rasterised polygons are wrong by a pixel or so), or inside the regions?  `edges` are distances in pixels
+    (1 to 8, finite, >= 0); a pixel of Euclidean distance d to the nearest boundary pixel falls into bin b = the number of edges with
+    d > edge, i.e. bin 0 holds d <= edges[0] and the last bin d > edges[-1] - and every pixel of a tile without any boundary.  The
+    comparison is made on squared distances, `dist2 > floor(edge^2)`, which is the same thing for integer dist2; the converted edges
+    must ascend strictly.  The boundaries are those of `classmap.distance_transform(labels, K, "boundary", connectivity,
+    exclude=(ignore_index,))`; the counts themselves ignore nothing (the CONFUSION convention: `ignore_index` acts in `compute()`), so
+    `total()` is exactly what `SegMetrics` accumulates over the same pairs.  The counts come from the launch that computes the
+    distances (csrc/distance.hip): exact integer sums, no separate CONFUSION pass."""
+
+    def __init__(self, num_classes: int, edges=(1, 2, 4, 8), ignore_index: int | None = 0, connectivity: int = 4, device=None):
+        self.C = CM.check_classes(num_classes)
+        self.thresholds = CM.check_edges(edges)
+        self.edges = [float(e) for e in edges]
+        self.connectivity = CM.check_connectivity(connectivity)
+        self.ignore_index = None if ignore_index is None else CM.check_ignore_index(ignore_index, self.C)
+        self.hist = torch.zeros(len(self.thresholds) + 1, self.C, self.C, dtype=torch.int64, device=device or "cuda")
+
+    @property
+    def num_classes(self) -> int:
+        return self.C
+
+    @property
+    def exclude(self) -> int:
+        return 0 if self.ignore_index is None else 1 << self.ignore_index
+
+    def reset(self) -> None:
+        self.hist.zero_()
+
+    @torch.no_grad()
+    def update(self, predictions: torch.Tensor, labels: torch.Tensor) -> None:
+        """predictions, labels: int64 [B, H, W] class ids on the GPU; `hist` is added to."""
+        if (not isinstance(predictions, torch.Tensor) or not isinstance(labels, torch.Tensor) or predictions.shape != labels.shape
+                or predictions.dtype != torch.int64 or labels.dtype != torch.int64 or labels.dim() != 3 or labels.numel() == 0):
+            raise ValueError("predictions and labels must be int64 [B, H, W] tensors of the same shape")
+        if labels.shape[1] > CM.EDT_MAX_DIM or labels.shape[2] > CM.EDT_MAX_DIM:
+            raise ValueError(f"the distance transform takes maps of at most {CM.EDT_MAX_DIM} x {CM.EDT_MAX_DIM}")
+        if not predictions.is_cuda or not labels.is_cuda:
+            raise RuntimeError("DistanceBinnedMetrics accumulates on the GPU (there is no CPU fallback)")
+        if self.hist.device != labels.device:
+            self.hist = self.hist.to(labels.device)
+        CM.count_by_distance(labels.contiguous(), predictions.contiguous(), self.C, self.connectivity, self.exclude, self.thresholds, self.hist)
+
+    def total(self) -> torch.Tensor:
+        """int64 [C, C] on the device: the counts of all bins together - `SegMetrics.hist` over the same pairs"""
+        return self.hist.sum(0)
+
+    def compute(self) -> list:
+        """one dict per bin: {"lo", "hi": the bin's bounds in pixels (lo < d <= hi; the first lo is 0 and inclusive, the last hi inf),
+        "pixels": the counted pairs, and the entries of `metrics_from_hist` over the bin's counts}"""
+        h = self.hist.cpu()
+        lo = [0.0] + self.edges
+        hi = self.edges + [float("inf")]
+        return [{"lo": lo[b], "hi": hi[b], "pixels": int(h[b].sum()), **metrics_from_hist(h[b], self.ignore_index)} for b in range(h.shape[0])]

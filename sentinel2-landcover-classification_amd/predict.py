@@ -13,6 +13,7 @@ a gather with a fixed summation order, so a prediction is bit-identical from run
     metrics.compute()                                                   # whole-tile IoU / accuracy / F1
     class_map = predictor.predict([3, 17], majority=5)                  # after the 5 x 5 majority filter (classmap.py); so evaluate, render
     class_map = predictor.predict([3, 17], majority=5, min_area=16)     # then without its patches below 16 pixels (classmap.sieve)
+    predictor.evaluate_by_distance(binned)                              # confusion counts by distance to the label boundaries (metrics.DistanceBinnedMetrics)
 """
 from __future__ import annotations
 
@@ -148,6 +149,31 @@ class TilePredictor:
             mask = CM.run_majority(mask, self.K, size, its, CM.class_bits(None, self.K, "votes"), 0, last=None if area is not None else last)
         if area is not None:
             CM.run_sieve(mask, self.K, area, conn, 1, 0, -1, last=last)
+
+    @torch.no_grad()
+    def evaluate_by_distance(self, binned, indices=None, majority: int | None = None, iterations: int = 1, min_area: int | None = None,
+                             connectivity: int = 4) -> None:
+        """Add the confusion counts of the selected tiles, binned by the distance of every pixel to the nearest class boundary of the
+        pipeline's resident labels, into `binned.hist` (a `metrics.DistanceBinnedMetrics`).  The class maps are those of
+        `predict(indices, majority, iterations, min_area, connectivity)`; the labels are the gathered uint8 labels read through the
+        pipeline's label table inside the kernel (no int64 label tensor is built), and the counts come from the launch that computes
+        the distances.  The boundaries follow `binned.connectivity`; `connectivity` is the sieve's."""
+        if int(binned.num_classes) != self.K:
+            raise ValueError("binned.num_classes differs from the predictor's")
+        size, its, area, conn = self._post(majority, iterations, min_area, connectivity)
+        pipe = self.pipe
+        if pipe.raw is None:
+            raise RuntimeError("call load() first")
+        idx = pipe._stats_index(indices, need_labels=True)               # ValueError first, then the refusal to run off the GPU
+        mask = self._run(idx, want="mask")
+        if size is not None:
+            mask = CM.run_majority(mask, self.K, size, its, CM.class_bits(None, self.K, "votes"), 0)
+        if area is not None:
+            mask = CM.run_sieve(mask, self.K, area, conn, 1, 0, -1)
+        if binned.hist.device != pipe.device:
+            binned.hist = binned.hist.to(pipe.device)
+        labels = pipe.labels.index_select(0, idx.to(pipe.device))
+        CM.count_by_distance(labels, mask, self.K, binned.connectivity, binned.exclude, binned.thresholds, binned.hist, src_lut=pipe.lut)
 
     def render(self, indices, palette, alpha: float = 0.5, majority: int | None = None, iterations: int = 1, min_area: int | None = None,
                connectivity: int = 4) -> torch.Tensor:
