@@ -247,25 +247,21 @@ int launch_weight_pack(const S2kOp& op, const Ctx& c) {
     if (!table || !src || !dst || n <= 0 || total <= 0 || (total & 4095) || (total >> 12) > 0x7fffffff) {
         set_error("weight_pack: bad args (total must be a multiple of 4096: MP % 128 == 0, KP % 64 == 0)"); return S2K_EINVAL;
     }
+    // every refusal comes before the first launch: a refused record leaves DST as it was
+    const int64_t b16 = op.n[S2K_WEIGHT_PACK_N_BF16_BASE], q4 = op.n[S2K_WEIGHT_PACK_N_Q4_BASE], sb = op.n[S2K_WEIGHT_PACK_N_SPLIT_BASE];
+    if (b16 > 0 && (b16 & 15)) { set_error("weight_pack: BF16_BASE must be a multiple of 16 bytes"); return S2K_EINVAL; }
+    if (q4 > 0 && (q4 & 15)) { set_error("weight_pack: Q4_BASE must be a multiple of 16 bytes"); return S2K_EINVAL; }
+    if (sb > 0 && (sb & 15)) { set_error("weight_pack: SPLIT_BASE must be a multiple of 16 bytes"); return S2K_EINVAL; }
     hipLaunchKernelGGL(weight_pack_kernel, dim3((unsigned)(total >> 12)), dim3(NTHREADS), 0, c.stream, table, n, src, dst, total);
-    const int64_t b16 = op.n[S2K_WEIGHT_PACK_N_BF16_BASE];
-    if (b16 > 0) {
-        if (b16 & 15) { set_error("weight_pack: BF16_BASE must be a multiple of 16 bytes"); return S2K_EINVAL; }
+    if (b16 > 0)
         hipLaunchKernelGGL(weight_pack_bf16_kernel, dim3((unsigned)(total / (NTHREADS * 8))), dim3(NTHREADS), 0, c.stream, table, n,
                            dst, reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + b16));
-    }
-    const int64_t q4 = op.n[S2K_WEIGHT_PACK_N_Q4_BASE];
-    if (q4 > 0) {
-        if (q4 & 15) { set_error("weight_pack: Q4_BASE must be a multiple of 16 bytes"); return S2K_EINVAL; }
+    if (q4 > 0)
         hipLaunchKernelGGL(weight_pack_q4_kernel, dim3((unsigned)(total / (NTHREADS * 8))), dim3(NTHREADS), 0, c.stream, table, n,
                            dst, reinterpret_cast<float*>(reinterpret_cast<char*>(dst) + q4));
-    }
-    const int64_t sb = op.n[S2K_WEIGHT_PACK_N_SPLIT_BASE];
-    if (sb > 0) {
-        if (sb & 15) { set_error("weight_pack: SPLIT_BASE must be a multiple of 16 bytes"); return S2K_EINVAL; }
+    if (sb > 0)
         hipLaunchKernelGGL(weight_pack_split_kernel, dim3((unsigned)(total / (NTHREADS * 8))), dim3(NTHREADS), 0, c.stream, table, n,
                            dst, reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + sb));
-    }
     return S2K_OK;
 }
 

@@ -8,7 +8,9 @@ its bar per column / per channel (per_column, per_channel) and to leaving the re
 BatchNorm / SE / residual / reduction cases below are pinned to the family tests/ew_dispatch.py restates; their routing boundaries,
 loop edges and forms are covered row by row in tests/test_ew_kernels_gpu.py.  The f32 CONV cases are pinned to the family
 tests/conv_dispatch.py restates (checked on the CPU by tests/test_conv_dispatch_cpu.py); the four dense-convolution kernels are covered
-instantiation by instantiation in tests/test_conv_kernels_gpu.py."""
+instantiation by instantiation in tests/test_conv_kernels_gpu.py.  WEIGHT_PACK (here only a one-row table in front of a CONV, its
+regions exempt from `untouched`), WGRAD_FINALIZE, AXPY, MEMSET, SPACE_TO_DEPTH and IM2COL are held bit for bit, over the whole arena,
+in tests/test_pack_kernels_gpu.py against the layout reference tests/pack_ref.py (checked on the CPU by tests/test_pack_ref_cpu.py)."""
 import numpy as np
 import pytest
 import torch
@@ -835,7 +837,10 @@ def test_wgrad_finalize():
     tab = c.t("table", (len(table), 5), torch.tensor(table), "i32")
     wgs = c.t("wgs", (2048,))
     grads = c.t("grads", (2048,))
-    c.run("WGRAD_FINALIZE", ["grads"], 1e-6, TABLE=tab, WGS=wgs, GRADS=grads, TOTAL=start, N_ENTRIES=len(table))
+    # one f32 add per element: bit-equal to the oracle, and nothing outside GRADS written (gaps, search edges, the grid stride's
+    # second trip: tests/test_pack_kernels_gpu.py)
+    c.run("WGRAD_FINALIZE", ["grads"], 1e-30, untouched=True, TABLE=tab, WGS=wgs, GRADS=grads, TOTAL=start, N_ENTRIES=len(table))
+    assert torch.equal(c.read(c.got, "grads").view(torch.int32), c.read(c.ref, "grads").view(torch.int32))
 
 
 # ---------------------------------------------------------------------------------------------------
