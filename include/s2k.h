@@ -239,6 +239,53 @@ int s2k_classmap_distance(const void* src, int src_bytes, const int* src_lut, in
                           const int* edges, int n_edges, unsigned long long* hist, void* stream);
 size_t s2k_classmap_distance_workspace(int M, int H, int W);
 
+/* Calibration of a probability map: the confidence raster, the class map with an abstention class, the reliability histogram and the
+ * negative log-likelihood under several temperatures (metrics.CalibrationMetrics, metrics.fit_temperature, classmap.confidence;
+ * csrc/calibration.hip).  A plain function like s2k_classmap_distance, not a stage kind: the stage table stays at 55 kinds and
+ * S2K_ABI_VERSION at 2.  ONE launch on `stream`; every loop is bounded by construction (a workgroup walks a fixed number of passes).
+ *
+ * Inputs.  scores: f32 [N][K][P], the NCHW layout with P = H * W; 1 <= K <= 32.  mode 0: the scores are probabilities and are taken as
+ * given; mode 1: logits.  labels: uint8 (label_bytes == 1) or int64 (== 8) [N][P], or NULL; label_lut: int32[256] or NULL, only with
+ * 1-byte labels: the class of a pixel is then label_lut[raw].  exclude: bit mask of label classes that are not counted.  temps:
+ * f32[n_temps] in HOST memory, 1 <= n_temps <= 8, each finite and above 0 (mode 0: the single value 1); the kernel multiplies by
+ * r_t = 1.0f / temps[t], rounded once on the host.  1 <= bins <= 64.  measure 0 max, 1 margin.  reject_to: a class in [0, K), or -1.
+ * Outputs, each may be NULL, at least one is required; device pointers, borrowed:
+ *   conf f32 [N][P];  pred uint8 or int64 [N][P] (pred_bytes);  hist u64 [K][bins][3], ADDED to;  totals u64 [n_temps][2], ADDED to;
+ *   skipped u64 [1], ADDED to.  hist and totals need labels.
+ *
+ * Definitions (they are the oracle; the reference project has no such operation), per pixel with scores s[0..K):
+ *   a      the first maximum of s: top = s[0], then for k = 1..K-1 in order `if (s[k] > top)` - strict >, WINDOW_BLEND's ARGMAX rule; a
+ *          NaN is therefore never chosen over s[0].  Taken on the raw scores in both modes (T > 0 keeps the order).
+ *   mode 0 p[k] = s[k].  c = p[a].  nll_0 = 128 if !(p[label] > 0) (a score <= 0, or NaN), else -logf(p[label]).
+ *   mode 1 d[k] = s[k] - s[a] (f32; 0 at a); under temperature t: e[k] = expf(d[k] * r_t), S = e[0] + ... + e[K-1] added in index
+ *          order, p_t[k] = e[k] / S.  c = 1.0f / S under temps[0].  nll_t = logf(S) - d[label] * r_t, which is logsumexp(z) - z[label]
+ *          with the maximum taken out of both.  One rounding per written operator (no contraction).
+ *   c      is ALWAYS the binning confidence, whatever `measure` says.
+ *   conf   the written value: c for measure 0; for measure 1 c - second with second = the largest p[k], k != a (scanned from -infinity
+ *          with strict >; mode 1: (largest e[k], k != a) / S under temps[0]), and c itself when K == 1.
+ *   pred   (reject_to >= 0 && conf < reject_below) ? reject_to : a.  A NaN conf is never below anything.  Rejection never affects the
+ *          counts: the histogram is that of a.
+ *   A pixel is COUNTED if its label class (after the table) lies in [0, K), its class bit is not set in exclude, and 0 <= c <= 1.  A
+ *   labelled pixel that fails only the last test (c above 1, negative or NaN) adds 1 to skipped[0].  For a counted pixel, with
+ *   b = min(bins - 1, (int)(c * (float)bins)) (an f32 product, truncated):
+ *     hist[a][b][0] += 1;  hist[a][b][1] += (label == a);  hist[a][b][2] += rint(c * 2^20)
+ *     for every t: totals[t][0] += 1;  totals[t][1] += rint(min(max(nll_t, 0), 128) * 2^20)   (a NaN nll_t counts as 0)
+ * Given the per-pixel c every sum is an integer function: exact, independent of the launch geometry and bit-identical from run to run.
+ * In mode 0 c itself is exact (a copy; the margin is one f32 subtraction); only nll in mode 0, and c and nll in mode 1, go through expf
+ * and logf.
+ * Every argument is validated on the host before anything is launched: S2K_EFAULT for a NULL scores; S2K_EINVAL for mode or measure
+ * other than 0 or 1, K outside 1..32, bins outside 1..64, n_temps outside 1..8, temps NULL, a temperature (or its f32 reciprocal) that is
+ * not finite and above 0, mode 0 with temps other than {1}, label_bytes (with labels) or pred_bytes (with pred) other than 1 or 8,
+ * label_lut without 1-byte labels, bits of exclude at K or above, reject_to outside -1..K-1, hist or totals without labels, no output at
+ * all, N or P below 1, N * ceil(P / 4) >= 2^31 (a thread owns a quad of pixels; at most 1024 workgroups walk the quads, and a
+ * workgroup's 32-bit counter halves then hold whatever it sees).  Messages begin with "calibration: ".  Quad loads and stores are used
+ * when P % 4 == 0 and scores, labels, conf and pred are 16-byte aligned; otherwise every element is read and written on its own.  No
+ * allocation, no copy, no synchronisation. */
+int s2k_calibration(const float* scores, int mode, const void* labels, int label_bytes, const int* label_lut, int N, int K, int P,
+                    unsigned exclude, const float* temps, int n_temps, int bins, int measure, float reject_below, int reject_to, float* conf,
+                    void* pred, int pred_bytes, unsigned long long* hist, unsigned long long* totals, unsigned long long* skipped,
+                    void* stream);
+
 /* Measured ceilings of the current device for roofline reporting (bench.py): sustained v_mfma_f32_32x32x2_f32 rate with every
  * SIMD issuing back to back (TFLOP/s), the shader clock held meanwhile (MHz), and a float4 stream copy (GB/s, read + write).
  * `scratch`: >= 64 MiB of device memory (size the copy past the caches: 1 GiB+).  Synchronises `stream`.  Not on the hot path. */

@@ -68,6 +68,8 @@ def lib() -> ctypes.CDLL:
     L.s2k_classmap_distance.argtypes = [vp, i32, vp] + [i32] * 5 + [u32, i32, u32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
     L.s2k_classmap_distance_workspace.restype = ctypes.c_size_t
     L.s2k_classmap_distance_workspace.argtypes = [i32] * 3
+    L.s2k_calibration.restype = i32
+    L.s2k_calibration.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, u32, vp, i32, i32, i32, ctypes.c_float, i32, vp, vp, i32, vp, vp, vp, vp]
     if L.s2k_abi_version() != 2:
         raise S2kError(f"libs2k ABI {L.s2k_abi_version()} != 2")
     if L.s2k_op_size() != D.OP_BYTES or OP_DTYPE.itemsize != D.OP_BYTES:
@@ -226,6 +228,25 @@ def classmap_distance(src, src_lut, dims, mode: int, sites: int, connectivity: i
 def classmap_distance_workspace(M: int, H: int, W: int) -> int:
     """bytes of the `work` buffer of s2k_classmap_distance for M maps of H x W"""
     return int(lib().s2k_classmap_distance_workspace(int(M), int(H), int(W)))
+
+
+CALIBRATION_MODES = {"probs": 0, "logits": 1}      # what the scores of s2k_calibration are (include/s2k.h)
+CALIBRATION_MEASURES = {"max": 0, "margin": 1}     # the written confidence
+
+
+def calibration(scores, mode: int, labels, label_lut, dims, exclude: int, temps, bins: int, measure: int, reject_below: float,
+                reject_to: int, conf, pred, hist, totals, skipped, stream: int, label_bytes: int | None = None,
+                pred_bytes: int | None = None, n_temps: int | None = None) -> int:
+    """s2k_calibration (include/s2k.h) as it is: tensors (or None) for the eight device pointers, dims = (N, K, P), `temps` a sequence
+    of floats (host memory) or None.  Returns the library's code; the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    lb = (8 if labels is None else labels.element_size()) if label_bytes is None else int(label_bytes)
+    pb = (8 if pred is None else pred.element_size()) if pred_bytes is None else int(pred_bytes)
+    nt = (0 if temps is None else len(temps)) if n_temps is None else int(n_temps)
+    arr = None if temps is None else (ctypes.c_float * max(len(temps), 1))(*[float(t) for t in temps])
+    return lib().s2k_calibration(ptr(scores), int(mode), ptr(labels), lb, ptr(label_lut), *[int(d) for d in dims], int(exclude) & 0xffffffff,
+                                 arr, nt, int(bins), int(measure), float(reject_below), int(reject_to), ptr(conf), ptr(pred), pb, ptr(hist),
+                                 ptr(totals), ptr(skipped), stream)
 
 
 MAE_PANELS = {"original": 0, "masked": 1, "pasted": 2, "reconstruction": 3}      # panel codes of s2k_mae_panels (include/s2k.h)

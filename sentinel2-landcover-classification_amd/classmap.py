@@ -45,6 +45,16 @@ tie rule (the smallest linear index).  Every loop of the kernels is bounded by i
 
 `GpuTilePipeline.ignore_label_boundaries_within`, `metrics.DistanceBinnedMetrics` and `TilePredictor.evaluate_by_distance` are built on
 them.
+
+All of the above read a class map, and a class map does not say how SURE it is.  `confidence` turns [B, K, H, W] probabilities or
+logits into the class map and a confidence raster - the largest probability, or its margin over the runner-up - and can put every pixel
+below a confidence into an abstention class (csrc/calibration.hip, one launch; the definitions are in include/s2k.h at
+s2k_calibration).  Whether that confidence means anything is `metrics.CalibrationMetrics`' question, from the same launch.
+
+    class_map, conf = confidence(probs)                                      # int64 [B, H, W], float32 [B, H, W]
+    class_map, conf = confidence(logits, "logits", "margin", temperature=1.7, min_confidence=0.2, reject_to=0, dtype=torch.uint8)
+
+`TilePredictor.predict_with_confidence` and `evaluate_calibration` are built on it.
 """
 from __future__ import annotations
 
@@ -495,3 +505,94 @@ def fill_nearest(class_map, num_classes: int, fill) -> torch.Tensor:
     near = nearest.view(M, H * W).long()
     taken = torch.gather(flat, 1, near.clamp(min=0))
     return torch.where(holes & (near >= 0), taken, flat).view(class_map.shape)
+
+
+# ---- confidence, abstention and the calibration sums (csrc/calibration.hip) -----------------------------------------------------------------
+CAL_MAX_BINS, CAL_MAX_TEMPS = 64, 8
+CAL_ONE = 1 << 20               # the quantum of the confidence and NLL sums: 2^-20 per pixel
+CAL_MAX_GRID = 1024             # workgroups of one launch; a workgroup walks passes of 256 pixel quads
+KINDS, MEASURES = _lib.CALIBRATION_MODES, _lib.CALIBRATION_MEASURES
+
+
+def check_kind(kind) -> int:
+    if kind not in KINDS:
+        raise ValueError('kind must be "probs" or "logits"')
+    return KINDS[kind]
+
+
+def check_measure(measure) -> int:
+    if measure not in MEASURES:
+        raise ValueError('measure must be "max" or "margin"')
+    return MEASURES[measure]
+
+
+def check_bins(bins) -> int:
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= CAL_MAX_BINS:
+        raise ValueError(f"bins must be an integer in 1..{CAL_MAX_BINS}")
+    return bins
+
+
+def check_temperature(temperature, kind: int = 1) -> float:
+    """a finite temperature above 0 whose float32 value and reciprocal are too; probabilities (kind 0) take 1 only"""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or not 1e-30 <= temperature <= 1e30:
+        raise ValueError("temperature must be a finite number in [1e-30, 1e30]")
+    if kind == 0 and temperature != 1:
+        raise ValueError("probabilities are taken as given: temperature must be 1 (scale the logits instead)")
+    return float(temperature)
+
+
+def check_scores(scores) -> torch.Tensor:
+    """[N, K, H, W] view of float32 scores given as [N, K, H, W] or [K, H, W]"""
+    if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32:
+        raise ValueError("scores must be a float32 tensor")
+    if scores.dim() not in (3, 4) or scores.numel() == 0:
+        raise ValueError("scores must be [B, K, H, W] or [K, H, W] and not empty")
+    s = scores.contiguous()
+    s = s.view(1, *s.shape) if s.dim() == 3 else s
+    check_classes(int(s.shape[1]))
+    if s.shape[2] * s.shape[3] >= 1 << 31 or s.shape[0] * ((s.shape[2] * s.shape[3] + 3) // 4) >= 1 << 31:
+        raise ValueError("scores: H * W and B * ceil(H * W / 4) must stay below 2^31")
+    return s
+
+
+def launch_calibration(scores, kind: int, temps, bins: int = 1, measure: int = 0, labels=None, label_lut=None, exclude: int = 0,
+                       reject_below: float = 0.0, reject_to: int = -1, conf=None, pred=None, hist=None, totals=None, skipped=None) -> None:
+    """One s2k_calibration launch over `scores` ([N, K, H, W] float32) on its device and current stream; labels [N, H, W] uint8 / int64."""
+    if not scores.is_cuda:
+        raise RuntimeError("calibration runs on the GPU (there is no CPU fallback)")
+    N, K, H, W = scores.shape
+    with torch.cuda.device(scores.device):
+        _lib.check(_lib.calibration(scores, kind, labels, label_lut, (N, K, H * W), exclude, temps, bins, measure, reject_below, reject_to,
+                                    conf, pred, hist, totals, skipped, torch.cuda.current_stream(scores.device).cuda_stream))
+
+
+@torch.no_grad()
+def confidence(scores, kind: str = "probs", measure: str = "max", temperature: float = 1.0, min_confidence=None, reject_to: int = 0,
+               dtype=torch.int64):
+    """(class_map, conf) of `scores` (float32 [B, K, H, W] or [K, H, W], on the GPU): the class of every pixel - the first maximum of its K
+    scores, the rule of `TilePredictor.predict` - as `dtype` (int64 or uint8), and a float32 confidence raster.  kind="probs": the scores
+    are probabilities and are taken as given; "logits": softmax(scores / temperature).  measure="max": the largest probability;
+    "margin": its lead over the runner-up.  min_confidence=c: every pixel whose confidence is below c becomes class `reject_to` in the
+    class map (an abstention; the reference's class 0, "other", is what its masked loss ignores).  One launch, scores read once."""
+    k, m = check_kind(kind), check_measure(measure)
+    T = check_temperature(temperature, k)
+    if dtype not in (torch.int64, torch.uint8):
+        raise ValueError("dtype must be torch.int64 or torch.uint8")
+    s = check_scores(scores)
+    K = int(s.shape[1])
+    to = -1
+    if min_confidence is not None:
+        if isinstance(min_confidence, bool) or not isinstance(min_confidence, (int, float)) or math.isnan(min_confidence):
+            raise ValueError("min_confidence must be None or a number")
+        to = check_to(reject_to, K)
+        if to < 0:
+            raise ValueError(f"reject_to must be a class id in [0, {K})")
+    if not s.is_cuda:
+        raise RuntimeError("calibration runs on the GPU (there is no CPU fallback)")
+    N, _, H, W = s.shape
+    pred = torch.empty(N, H, W, dtype=dtype, device=s.device)
+    conf = torch.empty(N, H, W, dtype=torch.float32, device=s.device)
+    launch_calibration(s, k, [T], measure=m, reject_below=0.0 if min_confidence is None else float(min_confidence), reject_to=to, conf=conf,
+                       pred=pred)
+    shape = scores.shape[:-3] + scores.shape[-2:]
+    return pred.view(shape), conf.view(shape)

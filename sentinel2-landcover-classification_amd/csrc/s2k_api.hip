@@ -106,6 +106,10 @@ int check_classmap_distance(const void*, int, const int*, int, int, int, int, in
 int launch_classmap_distance(const void*, int, const int*, int, int, int, int, int, unsigned, int, unsigned, void*, int*, int*, const void*, int,
                              const int*, int, unsigned long long*, hipStream_t);
 size_t classmap_distance_workspace(int, int, int);
+int check_calibration(const float*, int, const void*, int, const int*, int, int, int, unsigned, const float*, int, int, int, float, int, float*,
+                      void*, int, unsigned long long*, unsigned long long*, unsigned long long*);
+int launch_calibration(const float*, int, const void*, int, const int*, int, int, int, unsigned, const float*, int, int, int, float, int, float*,
+                       void*, int, unsigned long long*, unsigned long long*, unsigned long long*, hipStream_t);
 
 static int launch_memset(const S2kOp& op, const Ctx& c) {
     const int64_t ref = op.t[S2K_MEMSET_T_DST];
@@ -548,6 +552,23 @@ int s2k_classmap_distance(const void* src, int src_bytes, const int* src_lut, in
 }
 
 size_t s2k_classmap_distance_workspace(int M, int H, int W) { return classmap_distance_workspace(M, H, W); }
+
+int s2k_calibration(const float* scores, int mode, const void* labels, int label_bytes, const int* label_lut, int N, int K, int P,
+                    unsigned exclude, const float* temps, int n_temps, int bins, int measure, float reject_below, int reject_to, float* conf,
+                    void* pred, int pred_bytes, unsigned long long* hist, unsigned long long* totals, unsigned long long* skipped,
+                    void* stream) {
+    // every argument is validated before the first HIP call (the device guard's included)
+    const int bad = check_calibration(scores, mode, labels, label_bytes, label_lut, N, K, P, exclude, temps, n_temps, bins, measure, reject_below,
+                                      reject_to, conf, pred, pred_bytes, hist, totals, skipped);
+    if (bad != S2K_OK) return bad;
+    DeviceGuard guard(static_cast<hipStream_t>(stream));
+    const int rc = launch_calibration(scores, mode, labels, label_bytes, label_lut, N, K, P, exclude, temps, n_temps, bins, measure, reject_below,
+                                      reject_to, conf, pred, pred_bytes, hist, totals, skipped, static_cast<hipStream_t>(stream));
+    if (rc != S2K_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("calibration: %s", hipGetErrorString(e)); return S2K_EHIP; }
+    return S2K_OK;
+}
 
 int s2k_selftest_mfma(const float* a, const float* b, float* d, void* stream) {
     if (!a || !b || !d) { set_error("selftest: null pointer"); return S2K_EINVAL; }

@@ -14,6 +14,8 @@ a gather with a fixed summation order, so a prediction is bit-identical from run
     class_map = predictor.predict([3, 17], majority=5)                  # after the 5 x 5 majority filter (classmap.py); so evaluate, render
     class_map = predictor.predict([3, 17], majority=5, min_area=16)     # then without its patches below 16 pixels (classmap.sieve)
     predictor.evaluate_by_distance(binned)                              # confusion counts by distance to the label boundaries (metrics.DistanceBinnedMetrics)
+    class_map, conf = predictor.predict_with_confidence([3, 17], min_confidence=0.6)     # the confidence raster; unsure pixels become class 0
+    predictor.evaluate_calibration(cal)                                 # reliability, ECE and NLL of the blend (metrics.CalibrationMetrics)
 """
 from __future__ import annotations
 
@@ -174,6 +176,29 @@ class TilePredictor:
             binned.hist = binned.hist.to(pipe.device)
         labels = pipe.labels.index_select(0, idx.to(pipe.device))
         CM.count_by_distance(labels, mask, self.K, binned.connectivity, binned.exclude, binned.thresholds, binned.hist, src_lut=pipe.lut)
+
+    def predict_with_confidence(self, indices=None, measure: str = "max", min_confidence=None, reject_to: int = 0):
+        """(class_map int64 [M, H, W], conf float32 [M, H, W]) on the device, from `predict_blend(indices)` in one more launch
+        (`classmap.confidence`): the confidence is the largest blended probability (measure="max") or its lead over the runner-up
+        ("margin"); with blend="logits" the softmax of the blended logits is taken first.  min_confidence=c puts every pixel whose
+        confidence is below c into class `reject_to`.  Without it the class map is `predict(indices)` bit for bit: both take the first
+        maximum of the same stored values."""
+        CM.check_measure(measure)
+        return CM.confidence(self.predict_blend(indices), "probs" if self.mode == 1 else "logits", measure, 1.0, min_confidence, reject_to)
+
+    @torch.no_grad()
+    def evaluate_calibration(self, cal, indices=None) -> None:
+        """Add the calibration sums of the selected tiles' blend - `predict_blend(indices)`, as probabilities (blend="probs") or logits
+        under `cal.temperature` - against the pipeline's resident labels into `cal` (a `metrics.CalibrationMetrics`).  The labels are
+        the gathered uint8 labels read through the pipeline's label table inside the kernel: no int64 label tensor is built."""
+        if int(cal.num_classes) != self.K:
+            raise ValueError("cal.num_classes differs from the predictor's")
+        pipe = self.pipe
+        if pipe.raw is None:
+            raise RuntimeError("call load() first")
+        idx = pipe._stats_index(indices, need_labels=True)               # ValueError first, then the refusal to run off the GPU
+        blend = self._run(idx, want="blend")
+        cal.update(blend, pipe.labels.index_select(0, idx.to(pipe.device)), "probs" if self.mode == 1 else "logits", label_lut=pipe.lut)
 
     def render(self, indices, palette, alpha: float = 0.5, majority: int | None = None, iterations: int = 1, min_area: int | None = None,
                connectivity: int = 4) -> torch.Tensor:
