@@ -286,6 +286,50 @@ int s2k_calibration(const float* scores, int mode, const void* labels, int label
                     void* pred, int pred_bytes, unsigned long long* hist, unsigned long long* totals, unsigned long long* skipped,
                     void* stream);
 
+/* Exact polygon rasterisation into label tiles (classmap.PolygonSet, classmap.rasterize, GpuTilePipeline.rasterize_labels;
+ * csrc/rasterize.hip).  A plain function like s2k_calibration, not a stage kind: the stage table stays at 55 kinds and S2K_ABI_VERSION at
+ * 2.  Three plain launches on `stream` whatever the geometry looks like (boxes, per-tile lists, fill): no grid-wide barrier, no host read.
+ *
+ * Definitions (they are the oracle; the reference burns its labels with rasterio.features.rasterize on the host, whose tie rule on an
+ * edge is GDAL's own).  One pixel frame for the whole area of interest: x to the right, y down.  Pixel (i, j) of a tile with origin
+ * (ox, oy), in whole pixels, has its centre at (ox + j + 1/2, oy + i + 1/2).  Coordinates are fixed point, 256 units per pixel, i32: in
+ * units the centre is cx = 256 (ox + j) + 128, cy = 256 (oy + i) + 128.  Every vertex coordinate and every 256 * origin has magnitude at
+ * most 2^28; every product below then fits int64 (each is below 2^29 * 2^29).
+ *   verts       i32 [V][2]: (x, y) in units.
+ *   ring_start  i32 [R + 1]: ring r is the closed polyline over verts[ring_start[r] .. ring_start[r + 1]), the closing edge implied;
+ *               non-decreasing, ring_start[0] = 0, ring_start[R] = V.  A ring of fewer than 3 vertices covers nothing.
+ *   ring_shape  i32 [R]: the shape a ring belongs to; non-decreasing, in [0, S).  A SHAPE is the set of its rings - exterior, holes and
+ *               the parts of a multi-polygon alike; a shape without rings covers nothing.
+ *   INSIDE      a centre is inside a shape when the number of edges over all its rings with BOTH properties is odd (even-odd rule):
+ *               (1) ylo <= cy < yhi, (xlo, ylo) the end of the edge with the smaller y and (xhi, yhi) the other: horizontal edges never
+ *               count; (2) xlo * (yhi - ylo) + (cy - ylo) * (xhi - xlo) <= cx * (yhi - ylo), exactly, in int64: the crossing is not to
+ *               the right of the centre.  This is the top-left rule: a centre on a left or top edge is inside, one on a right or bottom
+ *               edge outside, so shapes that share an edge partition the centres on it.
+ *   ORDER       shapes are burned in index order; a pixel inside several takes the last.
+ *   values      i32 [S]: what shape s burns (burn == 0); with burn == 1 it burns s itself and values may be NULL.
+ *   origins     i32 [M][2]: (ox, oy) of tile m, a device pointer like the rest.
+ *   dst         [M][H][W], dst_bytes 1 (uint8), 4 (int32) or 8 (int64) an element; a burned value is stored by conversion (a 1-byte dst
+ *               takes its low byte).  mode 0 (fill): a pixel inside no shape gets `fill`; mode 1 (onto): it keeps what dst held.
+ *   unfilled    i64 [M] or NULL, ADDED to: the pixels of tile m inside no shape.
+ *   work        s2k_rasterize_workspace(M, S) bytes, written and read by the call: 8 ints per shape (box and ranges), M list lengths,
+ *               M * S list entries.  16-byte aligned; verts and origins 8-byte aligned.
+ *   status      u32 [1], OR-ed into: what only the device can see.  1 the ring tables are out of order or out of range, 2 a vertex
+ *               beyond +-2^28, 4 an origin beyond +-2^20.  The kernels clamp every index and coordinate they read, and every loop is
+ *               bounded by a count passed by value or a compile-time constant, so that such tables cause neither a read out of bounds
+ *               nor an endless loop; the output is then not to be used.
+ * Validated on the host before anything is launched: S2K_EFAULT for a NULL verts, ring_start, ring_shape, origins, dst, work or status
+ * (reported first); S2K_EINVAL for a misaligned verts, origins or work, V, R or S below 0, R > V, rings without a shape (R > 0, S == 0),
+ * vertices without a ring (R == 0, V > 0), dst_bytes other than 1, 4 or 8, mode or burn other than 0 or 1, burn == 1 with a 1-byte dst,
+ * burn == 0 with values NULL and S > 0, fill outside 0..255 with a 1-byte dst, M, H or W below 1, H * W >= 2^31 (offsets inside a tile are
+ * 32-bit; the tile offset is 64-bit), M * ceil(H / 32) * ceil(W / 512) >= 2^31 (one workgroup per 32 x 512 block of a tile).  V = 0,
+ * R = 0 and S = 0 are valid: every tile is `fill`, or dst is left as it is.  Messages begin with "rasterize: ".  The result is the
+ * definition bit for bit and identical from run to run.  No allocation, no copy, no synchronisation.
+ * s2k_rasterize_workspace: bytes of `work` (0 for M below 1 or S below 0). */
+int s2k_rasterize(const int* verts, int V, const int* ring_start, const int* ring_shape, int R, const int* values, int S, const int* origins,
+                  int M, int H, int W, void* dst, int dst_bytes, int mode, int burn, int fill, void* work, long long* unfilled, int* status,
+                  void* stream);
+size_t s2k_rasterize_workspace(int M, int S);
+
 /* Measured ceilings of the current device for roofline reporting (bench.py): sustained v_mfma_f32_32x32x2_f32 rate with every
  * SIMD issuing back to back (TFLOP/s), the shader clock held meanwhile (MHz), and a float4 stream copy (GB/s, read + write).
  * `scratch`: >= 64 MiB of device memory (size the copy past the caches: 1 GiB+).  Synchronises `stream`.  Not on the hot path. */

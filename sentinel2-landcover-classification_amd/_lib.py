@@ -70,6 +70,10 @@ def lib() -> ctypes.CDLL:
     L.s2k_classmap_distance_workspace.argtypes = [i32] * 3
     L.s2k_calibration.restype = i32
     L.s2k_calibration.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, u32, vp, i32, i32, i32, ctypes.c_float, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.s2k_rasterize.restype = i32
+    L.s2k_rasterize.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.s2k_rasterize_workspace.restype = ctypes.c_size_t
+    L.s2k_rasterize_workspace.argtypes = [i32] * 2
     if L.s2k_abi_version() != 2:
         raise S2kError(f"libs2k ABI {L.s2k_abi_version()} != 2")
     if L.s2k_op_size() != D.OP_BYTES or OP_DTYPE.itemsize != D.OP_BYTES:
@@ -247,6 +251,26 @@ def calibration(scores, mode: int, labels, label_lut, dims, exclude: int, temps,
     return lib().s2k_calibration(ptr(scores), int(mode), ptr(labels), lb, ptr(label_lut), *[int(d) for d in dims], int(exclude) & 0xffffffff,
                                  arr, nt, int(bins), int(measure), float(reject_below), int(reject_to), ptr(conf), ptr(pred), pb, ptr(hist),
                                  ptr(totals), ptr(skipped), stream)
+
+
+RASTERIZE_MODES = {"fill": 0, "onto": 1}           # what s2k_rasterize does with a pixel inside no shape (include/s2k.h)
+RASTERIZE_BURN = {"value": 0, "index": 1}          # what a shape burns
+
+
+def rasterize(verts, ring_start, ring_shape, values, origins, dst, dims, mode: int, burn: int, fill: int, work, unfilled, status, stream: int,
+              dst_bytes: int | None = None) -> int:
+    """s2k_rasterize (include/s2k.h) as it is: tensors (or None) for the nine pointers, dims = (V, R, S, M, H, W); the element width of
+    dst defaults to the tensor's own.  Returns the library's code; the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    V, R, S, M, H, W = (int(d) for d in dims)
+    db = (8 if dst is None else dst.element_size()) if dst_bytes is None else int(dst_bytes)
+    return lib().s2k_rasterize(ptr(verts), V, ptr(ring_start), ptr(ring_shape), R, ptr(values), S, ptr(origins), M, H, W, ptr(dst), db, int(mode),
+                               int(burn), int(fill), ptr(work), ptr(unfilled), ptr(status), stream)
+
+
+def rasterize_workspace(M: int, S: int) -> int:
+    """bytes of the `work` buffer of s2k_rasterize for M tiles and S shapes"""
+    return int(lib().s2k_rasterize_workspace(int(M), int(S)))
 
 
 MAE_PANELS = {"original": 0, "masked": 1, "pasted": 2, "reconstruction": 3}      # panel codes of s2k_mae_panels (include/s2k.h)

@@ -55,11 +55,27 @@ s2k_calibration).  Whether that confidence means anything is `metrics.Calibratio
     class_map, conf = confidence(logits, "logits", "margin", temperature=1.7, min_confidence=0.2, reject_to=0, dtype=torch.uint8)
 
 `TilePredictor.predict_with_confidence` and `evaluate_calibration` are built on it.
+
+And all of the above CONSUME label rasters.  The reference makes its own on the host, burning OSM polygons into 512 x 512 uint8 tiles
+with rasterio.features.rasterize (src/data/download_labels.py:203-227: the last of overlapping features wins, then the MAX_UNLABELED test
+on the share of pixels left at 0).  `PolygonSet` keeps the polygons resident and `rasterize` burns them into any number of tiles on the
+GPU (csrc/rasterize.hip, three launches whatever the geometry looks like; the definitions are in include/s2k.h at s2k_rasterize):
+fixed-point vertices, 256 units per pixel, the even-odd rule over half-open edges with the crossing compared exactly in int64 - the
+top-left rule, so polygons that share an edge partition the pixel centres on it.  Integer work with one exact answer.
+
+    ps = PolygonSet.from_geojson(geometries, values, west, north, xsize, ysize)         # or PolygonSet(shapes, values) in AOI pixels
+    labels, unfilled = rasterize(ps, origins, (512, 512), fill=0, return_unfilled=True)      # uint8 [M, 512, 512], int64 [M]
+    zones = rasterize(ps, origins, (512, 512), fill=-1, dtype=torch.int32, burn="index")      # the polygon index per pixel
+    rasterize(corrections, origins, fill=None, out=labels)                                    # burn onto what is there
+
+`GpuTilePipeline.rasterize_labels` is built on it.  How the result compares with GDAL's on real data has not been measured: it is
+expected to agree except within 1 / 512 pixel of an edge (the quantisation) and exactly on one (GDAL has its own tie rule).
 """
 from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -596,3 +612,266 @@ def confidence(scores, kind: str = "probs", measure: str = "max", temperature: f
                        pred=pred)
     shape = scores.shape[:-3] + scores.shape[-2:]
     return pred.view(shape), conf.view(shape)
+
+
+# ---- exact polygon rasterisation into label tiles (csrc/rasterize.hip) ------------------------------------------------------------------------
+RAST_Q = 256                    # fixed-point units per pixel
+RAST_MAX_COORD = 2 ** 28        # largest magnitude of a vertex coordinate, and of 256 * a tile origin, in units
+RAST_BLOCK_H, RAST_BLOCK_W = 32, 512    # the block of a tile one workgroup burns in LDS
+RAST_BOX_INTS = 8               # ints of workspace per shape: its box in units, its ring range and its vertex range
+RAST_DTYPES = (torch.uint8, torch.int32, torch.int64)
+FILL, ONTO = _lib.RASTERIZE_MODES["fill"], _lib.RASTERIZE_MODES["onto"]
+
+
+def quantise(coords) -> np.ndarray:
+    """int64 units of float64 AOI-pixel coordinates: floor(v * 256 + 0.5); ValueError for a value that is not finite or whose units
+    lie beyond +-RAST_MAX_COORD"""
+    v = np.asarray(coords, dtype=np.float64)
+    if not np.isfinite(v).all():
+        raise ValueError("coordinates must be finite")
+    q = np.floor(v * RAST_Q + 0.5)
+    if q.size and np.abs(q).max() > RAST_MAX_COORD:
+        raise ValueError(f"a coordinate lies beyond +-{RAST_MAX_COORD // RAST_Q} pixels (2^28 units)")
+    return q.astype(np.int64)
+
+
+def _ring(ring) -> np.ndarray:
+    try:
+        r = np.asarray(ring, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("a ring must be an [n, 2] array of coordinates") from None
+    if r.ndim != 2 or r.shape[1] != 2:
+        raise ValueError("a ring must be an [n, 2] array of coordinates")
+    return r
+
+
+class PolygonSet:
+    """Polygons in the pixel frame of an area of interest (x to the right, y down, pixel (i, j) of a tile at origin (ox, oy) centred at
+    (ox + j + 1/2, oy + i + 1/2)), quantised to 256 units per pixel and resident on `device` as the tables of s2k_rasterize
+    (include/s2k.h).  `shapes`: a sequence of shapes, each a sequence of rings - exterior, holes and the parts of a multi-polygon alike;
+    a centre is inside a shape by the even-odd rule over all of them - each ring an [n, 2] array-like of float64 (x, y) with n >= 3 and
+    the closing edge implied.  A shape without rings covers nothing.  `values`: one integer per shape (None: the set can only burn shape
+    indices).  Everything is checked and laid out in numpy on the host before the device is touched; the host copies stay in `host`."""
+
+    def __init__(self, shapes, values=None, device="cuda"):
+        try:
+            shapes = [list(rings) for rings in shapes]
+        except TypeError:
+            raise ValueError("shapes must be a sequence of shapes, each a sequence of rings") from None
+        rings = [[_ring(r) for r in sh] for sh in shapes]
+        if any(len(r) < 3 for sh in rings for r in sh):
+            raise ValueError("a ring needs at least 3 vertices (the closing edge is implied)")
+        flat = [r for sh in rings for r in sh]
+        verts = quantise(np.concatenate(flat, axis=0) if flat else np.zeros((0, 2))).astype(np.int32)
+        ring_start = np.zeros(len(flat) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in flat], out=ring_start[1:])
+        if ring_start[-1] >= 1 << 31:
+            raise ValueError("too many vertices (V must stay below 2^31)")
+        ring_shape = np.repeat(np.arange(len(rings), dtype=np.int32), [len(sh) for sh in rings]) if rings else np.zeros(0, np.int32)
+        if values is not None:
+            try:
+                vals = np.asarray(values)
+            except (TypeError, ValueError):
+                raise ValueError("values must be one integer per shape") from None
+            if vals.shape != (len(rings),) or (vals.size and vals.dtype.kind not in "iu"):
+                raise ValueError("values must be one integer per shape")
+            vals = vals.astype(np.int64)
+            if vals.size and (vals.min() < -(1 << 31) or vals.max() >= 1 << 31):
+                raise ValueError("values must fit int32")
+            values = vals.astype(np.int32)
+        self._shapes = len(rings)
+        self.host = {"verts": verts.reshape(-1, 2), "ring_start": ring_start.astype(np.int32), "ring_shape": ring_shape, "values": values}
+        self.device = torch.device(device)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)      # noqa: E731
+        # one spare element each: an empty table still has an address
+        self.verts = dev(np.concatenate([self.host["verts"], np.zeros((1, 2), np.int32)]))
+        self.ring_start = dev(self.host["ring_start"])
+        self.ring_shape = dev(np.concatenate([ring_shape, np.zeros(1, np.int32)]))
+        self.values = None if values is None else dev(np.concatenate([values, np.zeros(1, np.int32)]))
+
+    @classmethod
+    def from_world(cls, shapes, values, west: float, north: float, xsize: float, ysize: float, device="cuda") -> "PolygonSet":
+        """`shapes` in world coordinates through the reference's `from_origin(west, north, xsize, ysize)` transform:
+        px = (x - west) / xsize, py = (north - y) / ysize."""
+        for v in (west, north, xsize, ysize):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError("west, north, xsize and ysize must be finite numbers")
+        if xsize <= 0 or ysize <= 0:
+            raise ValueError("xsize and ysize must be positive")
+        try:
+            shapes = [list(rings) for rings in shapes]
+        except TypeError:
+            raise ValueError("shapes must be a sequence of shapes, each a sequence of rings") from None
+        out = []
+        for sh in shapes:
+            out.append([])
+            for ring in sh:
+                r = _ring(ring)
+                out[-1].append(np.stack([(r[:, 0] - west) / xsize, (north - r[:, 1]) / ysize], axis=1))
+        return cls(out, values, device)
+
+    @classmethod
+    def from_geojson(cls, geometries, values, west=None, north=None, xsize=None, ysize=None, device="cuda") -> "PolygonSet":
+        """One shape per GeoJSON-style geometry: a mapping {"type": "Polygon" | "MultiPolygon", "coordinates": ...} (what
+        `shapely.geometry.mapping` gives) or an object with `__geo_interface__`.  The repeated closing vertex of a ring is dropped;
+        coordinates beyond x and y are ignored.  Any other geometry type is a ValueError.  With west, north, xsize and ysize the
+        coordinates are world coordinates (`from_world`), without them AOI pixels."""
+        shapes = []
+        for g in geometries:
+            g = getattr(g, "__geo_interface__", g)
+            try:
+                kind, coords = g["type"], g["coordinates"]
+            except (TypeError, KeyError):
+                raise ValueError('a geometry must be a mapping with "type" and "coordinates"') from None
+            if kind == "Polygon":
+                polys = [coords]
+            elif kind == "MultiPolygon":
+                polys = list(coords)
+            else:
+                raise ValueError(f"geometry type {kind!r}: only Polygon and MultiPolygon are rasterised")
+            rings = []
+            for poly in polys:
+                for ring in poly:
+                    try:
+                        r = np.asarray(ring, dtype=np.float64)
+                    except (TypeError, ValueError):
+                        raise ValueError("a ring must be an [n, 2] array of coordinates") from None
+                    if r.ndim != 2 or r.shape[1] < 2:
+                        raise ValueError("a ring must be an [n, 2] array of coordinates")
+                    r = r[:, :2]
+                    if len(r) > 1 and np.array_equal(r[0], r[-1]):
+                        r = r[:-1]
+                    rings.append(r)
+            shapes.append(rings)
+        world = (west, north, xsize, ysize)
+        if all(v is None for v in world):
+            return cls(shapes, values, device)
+        if any(v is None for v in world):
+            raise ValueError("give west, north, xsize and ysize together, or none of them")
+        return cls.from_world(shapes, values, west, north, xsize, ysize, device)
+
+    @property
+    def num_shapes(self) -> int:
+        return self._shapes
+
+    @property
+    def num_rings(self) -> int:
+        return len(self.host["ring_shape"])
+
+    @property
+    def num_vertices(self) -> int:
+        return len(self.host["verts"])
+
+
+def rasterize_workspace_bytes(M: int, S: int) -> int:
+    """s2k_rasterize_workspace(M, S): RAST_BOX_INTS ints per shape, M list lengths, M * S list entries"""
+    return 4 * (RAST_BOX_INTS * S + M + M * S)
+
+
+def tiles_per_chunk(S: int, max_workspace_bytes: int) -> int:
+    """tiles whose workspace over S shapes stays within `max_workspace_bytes` (at least one)"""
+    return max(1, (max_workspace_bytes - 4 * RAST_BOX_INTS * S) // (4 * (S + 1)))
+
+
+def check_origins(origins, M=None):
+    """`origins` as an int32 [M, 2] tensor.  What lies on the host is range-checked here (256 * origin within +-RAST_MAX_COORD); a device
+    tensor is taken as it is: the kernels check it and report through the status word."""
+    if isinstance(origins, torch.Tensor):
+        o = origins
+        if o.dtype not in (torch.int32, torch.int64) or o.dim() != 2 or o.shape[1] != 2 or o.shape[0] < 1:
+            raise ValueError("origins must be an integer [M, 2] tensor or sequence of (ox, oy), M >= 1")
+    else:
+        try:
+            a = np.asarray(origins)
+        except (TypeError, ValueError):
+            raise ValueError("origins must be an integer [M, 2] tensor or sequence of (ox, oy), M >= 1") from None
+        if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1 or a.dtype.kind not in "iu":
+            raise ValueError("origins must be an integer [M, 2] tensor or sequence of (ox, oy), M >= 1")
+        o = torch.from_numpy(a.astype(np.int64))
+    if not o.is_cuda and int(o.abs().max()) > RAST_MAX_COORD // RAST_Q:
+        raise ValueError(f"an origin lies beyond +-{RAST_MAX_COORD // RAST_Q} pixels")
+    if M is not None and o.shape[0] != M:
+        raise ValueError(f"origins must hold one (ox, oy) per tile: {M}, got {o.shape[0]}")
+    return o.to(torch.int32).contiguous()
+
+
+def raise_rasterize_status(status: torch.Tensor) -> None:
+    """The one host read of a rasterisation: S2kError if the kernels met tables the host could not see."""
+    code = int(status.item())
+    if code:
+        raise _lib.S2kError(f"rasterize: status {code:#x} (1 ring tables out of order or range, 2 a vertex beyond 2^28 units, 4 an origin "
+                            "beyond 2^20 pixels): the outputs are not to be used")
+
+
+@torch.no_grad()
+def rasterize(polygons, origins, size=None, fill=0, out=None, dtype=torch.uint8, burn: str = "value", return_unfilled: bool = False,
+              max_workspace_bytes: int = 256 << 20):
+    """[M, H, W] rasters of `polygons` (a PolygonSet), one per tile origin (ox, oy) in `origins` ([M, 2] ints, a sequence or a tensor),
+    each of size = (H, W): a pixel whose centre is inside a shape - even-odd over the shape's rings, the top-left rule on its edges,
+    exact in fixed point (include/s2k.h at s2k_rasterize) - takes the value of the LAST such shape, as the reference's
+    rasterio.features.rasterize does; burn="index" burns the shape index instead (int32 / int64 only: a zone raster).  A pixel inside
+    no shape gets `fill`, in a new tensor of `dtype` (uint8, int32 or int64).  out=[M, H, W] (uint8, int32 or int64, contiguous, on the
+    GPU): burn ONTO it and leave the pixels inside no shape as they are; `fill` must then be None, and `size`, if given, out's own.
+    Values and fill must fit the raster's dtype.  return_unfilled=True adds int64 [M]: the pixels of every tile inside no shape (the
+    numerator of the reference's MAX_UNLABELED test).  The tiles are walked in chunks whose workspace (a list of candidate shapes per
+    tile) stays within `max_workspace_bytes`, at least one tile a chunk; three launches a chunk, and one status read at the end."""
+    if not isinstance(polygons, PolygonSet):
+        raise ValueError("polygons must be a PolygonSet")
+    if burn not in _lib.RASTERIZE_BURN:
+        raise ValueError('burn must be "value" or "index"')
+    if isinstance(max_workspace_bytes, bool) or not isinstance(max_workspace_bytes, int) or max_workspace_bytes < 1:
+        raise ValueError("max_workspace_bytes must be a positive integer")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype not in RAST_DTYPES or out.dim() != 3 or out.numel() == 0 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8, int32 or int64 [M, H, W] tensor")
+        if fill is not None:
+            raise ValueError("fill must be None with out: pixels inside no shape keep what out holds")
+        if size is not None and tuple(int(v) for v in size) != tuple(out.shape[1:]):
+            raise ValueError("size differs from out's")
+        dtype, (H, W) = out.dtype, out.shape[1:]
+    else:
+        if dtype not in RAST_DTYPES:
+            raise ValueError("dtype must be torch.uint8, torch.int32 or torch.int64")
+        try:
+            H, W = size
+        except (TypeError, ValueError):
+            raise ValueError("size must be (H, W)") from None
+        if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in (H, W)) or H * W >= 1 << 31:
+            raise ValueError("size must be (H, W), positive integers with H * W below 2^31")
+        lo, hi = (0, 255) if dtype == torch.uint8 else (-(1 << 31), (1 << 31) - 1)
+        if isinstance(fill, bool) or not isinstance(fill, int) or not lo <= fill <= hi:
+            raise ValueError(f"fill must be an integer in [{lo}, {hi}] for {dtype}")
+    o = check_origins(origins, None if out is None else out.shape[0])
+    M, S = int(o.shape[0]), polygons.num_shapes
+    if burn == "index":
+        if dtype == torch.uint8:
+            raise ValueError('burn="index" needs an int32 or int64 raster')
+    else:
+        vals = polygons.host["values"]
+        if vals is None:
+            raise ValueError('the PolygonSet holds no values: burn="index" is all it can do')
+        if dtype == torch.uint8 and vals.size and (vals.min() < 0 or vals.max() > 255):
+            raise ValueError("values must lie in 0..255 for a uint8 raster")
+    if M * ((H + RAST_BLOCK_H - 1) // RAST_BLOCK_H) * ((W + RAST_BLOCK_W - 1) // RAST_BLOCK_W) >= 1 << 31:
+        raise ValueError("too many tiles for one call")
+    if not polygons.verts.is_cuda or (out is not None and not out.is_cuda):
+        raise RuntimeError("polygons are rasterised on the GPU (there is no CPU fallback)")
+    dev = polygons.device
+    if out is not None and out.device != polygons.verts.device:
+        raise ValueError("out and the polygons are on different devices")
+    o = o.to(dev)
+    dst = out if out is not None else torch.empty(M, H, W, dtype=dtype, device=dev)
+    unfilled = torch.zeros(M, dtype=torch.int64, device=dev) if return_unfilled else None
+    status = new_status(dev)
+    step = min(M, tiles_per_chunk(S, max_workspace_bytes))
+    work = torch.empty(rasterize_workspace_bytes(step, S) // 4, dtype=torch.int32, device=dev)
+    mode, b = (ONTO if out is not None else FILL), _lib.RASTERIZE_BURN[burn]
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for m0 in range(0, M, step):
+            m1 = min(m0 + step, M)
+            _lib.check(_lib.rasterize(polygons.verts, polygons.ring_start, polygons.ring_shape, polygons.values, o[m0:m1], dst[m0:m1],
+                                      (polygons.num_vertices, polygons.num_rings, S, m1 - m0, H, W), mode, b, 0 if fill is None else fill, work,
+                                      None if unfilled is None else unfilled[m0:m1], status, stream))
+    raise_rasterize_status(status)
+    return (dst, unfilled) if return_unfilled else dst

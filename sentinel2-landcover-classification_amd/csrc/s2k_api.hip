@@ -110,6 +110,11 @@ int check_calibration(const float*, int, const void*, int, const int*, int, int,
                       void*, int, unsigned long long*, unsigned long long*, unsigned long long*);
 int launch_calibration(const float*, int, const void*, int, const int*, int, int, int, unsigned, const float*, int, int, int, float, int, float*,
                        void*, int, unsigned long long*, unsigned long long*, unsigned long long*, hipStream_t);
+int check_rasterize(const int*, int, const int*, const int*, int, const int*, int, const int*, int, int, int, void*, int, int, int, int, void*,
+                    long long*, int*);
+int launch_rasterize(const int*, int, const int*, const int*, int, const int*, int, const int*, int, int, int, void*, int, int, int, int, void*,
+                     long long*, int*, hipStream_t);
+size_t rasterize_workspace(int, int);
 
 static int launch_memset(const S2kOp& op, const Ctx& c) {
     const int64_t ref = op.t[S2K_MEMSET_T_DST];
@@ -569,6 +574,24 @@ int s2k_calibration(const float* scores, int mode, const void* labels, int label
     if (e != hipSuccess) { set_error("calibration: %s", hipGetErrorString(e)); return S2K_EHIP; }
     return S2K_OK;
 }
+
+int s2k_rasterize(const int* verts, int V, const int* ring_start, const int* ring_shape, int R, const int* values, int S, const int* origins,
+                  int M, int H, int W, void* dst, int dst_bytes, int mode, int burn, int fill, void* work, long long* unfilled, int* status,
+                  void* stream) {
+    // every argument is validated before the first HIP call (the device guard's included)
+    const int bad = check_rasterize(verts, V, ring_start, ring_shape, R, values, S, origins, M, H, W, dst, dst_bytes, mode, burn, fill, work,
+                                    unfilled, status);
+    if (bad != S2K_OK) return bad;
+    DeviceGuard guard(static_cast<hipStream_t>(stream));
+    const int rc = launch_rasterize(verts, V, ring_start, ring_shape, R, values, S, origins, M, H, W, dst, dst_bytes, mode, burn, fill, work,
+                                    unfilled, status, static_cast<hipStream_t>(stream));
+    if (rc != S2K_OK) return rc;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("rasterize: %s", hipGetErrorString(e)); return S2K_EHIP; }
+    return S2K_OK;
+}
+
+size_t s2k_rasterize_workspace(int M, int S) { return rasterize_workspace(M, S); }
 
 int s2k_selftest_mfma(const float* a, const float* b, float* d, void* stream) {
     if (!a || !b || !d) { set_error("selftest: null pointer"); return S2K_EINVAL; }

@@ -313,6 +313,44 @@ class GpuTilePipeline:
         self.lut = torch.arange(256, dtype=torch.int32).to(self.device)
 
     @torch.no_grad()
+    def rasterize_labels(self, polygons, origins, fill: int = 0, onto: bool = False) -> torch.Tensor:
+        """Build the resident labels from polygons (`classmap.PolygonSet`) whose values are CLASSES of the pipeline's label map - what
+        the reference does on the host with rasterio.features.rasterize (src/data/download_labels.py:203-227), here for every resident
+        tile at once and under whatever tag-to-class mapping the values were made with.  `origins`: one (ox, oy) per resident tile, the
+        tile's corner in the polygons' pixel frame.  A pixel inside several polygons takes the last; one inside none gets class `fill`.
+        onto=True: the current labels are first taken through the label table and the polygons are burned over them, pixels inside no
+        polygon keeping their class (`fill` is not used and must be left at 0) - corrections, or a mask: a value equal to the ignored
+        class masks a polygon out.  The labels become uint8 classes and the label table the identity; both tensors are REPLACED, not
+        written, exactly as `ignore_label_boundaries` documents.  Works on a pipeline loaded without labels (onto=False only).
+        Returns int64 [N] on the device: the pixels of every tile inside no polygon, the numerator of the reference's MAX_UNLABELED
+        test."""
+        if not isinstance(polygons, CM.PolygonSet):
+            raise ValueError("polygons must be a classmap.PolygonSet")
+        if self.raw is None:
+            raise RuntimeError("call load() first")
+        N, _, H, W = self.raw.shape
+        vals = polygons.host["values"]
+        if vals is None or (vals.size and (vals.min() < 0 or vals.max() >= self.label_classes)):
+            raise ValueError(f"the polygons' values must be classes of the label map: in [0, {self.label_classes})")
+        if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill < self.label_classes:
+            raise ValueError(f"fill must be a class id in [0, {self.label_classes})")
+        if onto and self.labels is None:
+            raise ValueError("the pipeline was loaded without labels: there is nothing to burn onto")
+        if onto and fill != 0:
+            raise ValueError("fill is not used with onto=True: leave it at 0")
+        o = CM.check_origins(origins, N)
+        if not self.raw.is_cuda:
+            raise RuntimeError("GpuTilePipeline runs on the GPU (there is no CPU fallback)")
+        if onto:
+            base = self.lut[self.labels.long()].to(torch.uint8)      # a new tensor; a table value outside a byte is stored as its low byte
+            new, unfilled = CM.rasterize(polygons, o, fill=None, out=base, return_unfilled=True)
+        else:
+            new, unfilled = CM.rasterize(polygons, o, (H, W), fill=fill, dtype=torch.uint8, return_unfilled=True)
+        self.labels = new
+        self.lut = torch.arange(256, dtype=torch.int32).to(self.device)
+        return unfilled
+
+    @torch.no_grad()
     def label_components(self, num_classes: int | None = None, indices=None, connectivity: int = 4) -> torch.Tensor:
         """int64 [M, num_classes] on the device: per selected tile (None = every resident tile), how many connected regions each class
         (after the label map's remap) forms - the patch count behind the pixel counts of `label_histogram`.  num_classes=None: the
