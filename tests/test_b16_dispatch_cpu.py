@@ -293,6 +293,23 @@ def test_declined_rows_are_declined_or_refused():
             assert v.result == "error" and v.message, T.rid(r)
         if v.result == "declined" and r["kind"] == "CONV":
             assert T.f32_family(r) in (0, 1, 3, 4)
+        if v.result == "declined" and r["kind"] == "WGRAD":     # pinned to the f32 family, or refused by the f32 launcher with the row's message
+            f = T.f32_launch(r)
+            assert (f.result in (0, 1, 4) and not r["raises"]) or (f.result == "error" and r["raises"] and re.search(r["raises"], f.message)), (T.rid(r), f.result, f.message)
+
+
+def test_f32_has_is_the_prologue_rule_of_the_f32_ladder():
+    """f32_has asks tests/wgrad_dispatch.py; on the tables' rows that is launch_wg's rule: a prologue on one side at most, never AFFINE;
+    3x3: none or ReLU on Q"""
+    NO, SI, RE, GE = BD.PRO_NONE, BD.PRO_SILU, BD.PRO_RELU, BD.PRO_GELU
+    rows = [r for tab in T.TABLES.values() for r in tab if r["kind"] == "WGRAD" and not r["p16"] and not r["gatep"] and not r["raises"]]
+    assert len(rows) >= 60
+    for r in rows:
+        if r["k"] == 3:
+            rule = r["prop"] == NO and r["proq"] in (NO, RE)
+        else:
+            rule = (r["prop"] == NO and r["proq"] in (NO, RE, SI, GE)) or (r["proq"] == NO and r["prop"] in (RE, SI, GE))
+        assert T.f32_has(r) == rule, T.rid(r)
 
 
 def test_tables_reach_every_reachable_instantiation():

@@ -8,8 +8,8 @@ launchers; tests/test_b16_dispatch_cpu.py checks without a GPU that the tables r
 produce at default tuning and every edge it lists.  Output channel c (CONV) / column c (WGRAD) is scaled by 2^-(c mod 8), so that a
 value in the wrong channel, or an error in one row of a tile, shows against that channel's own max |ref|.  Every row is held
 
-  * to the kernel family the launcher must take: 2, 5, or on a decline the f32 family tests/conv_dispatch.py restates (WGRAD: any f32
-    family - no restatement of that chain exists);
+  * to the kernel family the launcher must take: 2, 5, or on a decline the f32 family tests/conv_dispatch.py (CONV) or
+    tests/wgrad_dispatch.py (WGRAD) restates;
   * to leaving every byte of the arena outside the stage's outputs as uploaded (Y is NaN-filled or, with YC > M, a channel slice of
     a wider tensor whose other channels must stay bit-identical; WGS columns outside the stage's slice likewise).
 
@@ -53,6 +53,7 @@ from s2lc_amd.plan import opdefs as D
 from s2lc_amd.plan.program import Program
 from tests import b16_dispatch as BD
 from tests import conv_dispatch as CD
+from tests import wgrad_dispatch as WD
 from tests.test_ops_gpu import WS, Case
 
 NO, AF, SI, RE, GE = D.PRO_NONE, D.PRO_AFFINE, D.PRO_SILU, D.PRO_RELU, D.PRO_GELU
@@ -238,24 +239,26 @@ def launch(r):
     return BD.conv(**record(r)) if r["kind"] == "CONV" else BD.wgrad(**record(r))
 
 
-def f32_family(r):
-    """the kernel family that takes a declined CONV row (tests/conv_dispatch.py); None for WGRAD"""
-    if r["kind"] != "CONV":
-        return None
+def f32_launch(r):
+    """the f32 launchers' verdict on a row without its flag: tests/conv_dispatch.py (CONV) / tests/wgrad_dispatch.py (WGRAD; every
+    allocation of a Case is 16-byte aligned)"""
     rec = record(r)
-    rec.pop("X1_BF16")
+    rec.pop("X1_BF16" if r["kind"] == "CONV" else "P_BF16")
     rec["flags"] = 0
-    return CD.dispatch(**rec).family
+    return CD.dispatch(**rec) if r["kind"] == "CONV" else WD.dispatch(**rec)
+
+
+def f32_family(r):
+    """the kernel family that takes a declined row (tests/conv_dispatch.py, tests/wgrad_dispatch.py)"""
+    return f32_launch(r).family
 
 
 def f32_has(r) -> bool:
-    """the exact-f32 kernels instantiate the row's prologue pair (csrc/wgrad.hip launch_wg: a prologue on one side at most, never
-    AFFINE; 3x3: none or ReLU on Q), so that the f32-split scheme has its third leg"""
+    """the exact-f32 kernels take the row (tests/wgrad_dispatch.py: launch_wg instantiates a prologue on one side at most, never AFFINE;
+    3x3: none or ReLU on Q), so that the f32-split scheme has its third leg"""
     if r["kind"] == "CONV":
         return True
-    if r["k"] == 3:
-        return r["prop"] == NO and r["proq"] in (NO, RE)
-    return (r["prop"] == NO and r["proq"] in (NO, RE, SI, GE)) or (r["proq"] == NO and r["prop"] in (RE, SI, GE))
+    return f32_launch(r).result != "error"
 
 
 def row_edges(r) -> frozenset:

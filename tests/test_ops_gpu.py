@@ -666,6 +666,8 @@ def test_wgrad_3x3_bf16(B, M, C, CT, c_off, H, W, proq):
 # wgrad_pc_kernel's pixel mode (family 1: M, C > 32, B * H * W >= 1024, no gate, prologues (-, -), (-, ReLU), (ReLU, -)), then the
 # generic kernels (family 0).  Both faster kernels pick their tile by edge(n) per side: 128 where n > 64 and 128-channel tiles pad n
 # by at most 12 %, else 64 - (WM, WN) = (2, 2) for M 240 x C 250, (2, 1) for 240 x 144, (1, 2) for 144 x 240, (1, 1) for 40 x 176.
+# tests/wgrad_dispatch.py restates the whole chain (checked on the CPU by tests/test_wgrad_dispatch_cpu.py, which also holds the family
+# pins below to it); the three kernels are covered instantiation by instantiation in tests/test_wgrad_kernels_gpu.py.
 @pytest.mark.parametrize("B,M,C,H,W,proq,gate", [(2, 40, 144, 16, 16, 2, True), (3, 144, 24, 12, 12, 0, False),
                                                    (2, 4, 32, 16, 16, 3, False), (3, 200, 130, 7, 7, 0, False)])
 def test_wgrad_1x1(B, M, C, H, W, proq, gate):
