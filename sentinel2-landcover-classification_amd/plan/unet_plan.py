@@ -875,8 +875,10 @@ def finish_plan(p: "_P", layout: ParamLayout, training: bool, bucket_floats: int
         attach_q4()
         if not bwd_pack_in_fwd:
             pack_op(p.bwd, p.pack_rows["bwd"])
-        if len(p.bwd.ops) > n_before:   # WEIGHT_PACK went in front
-            segments = [(a + 1 if a else 0, b + 1, lo, hi) for (a, b, lo, hi) in segments]
+        if len(p.bwd.ops) > n_before:   # WEIGHT_PACK went in front: it belongs to the first segment that runs anything (a leading
+            # segment without stages - parameters at the top of the buffer that get no gradient, as in the encoder-only method
+            # plans - stays empty instead of becoming a second [0, 1))
+            segments = [(a + 1 if a else 0, b + 1 if b else 0, lo, hi) for (a, b, lo, hi) in segments]
         bwd = p.bwd
     else:
         attach_q4()

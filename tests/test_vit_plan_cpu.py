@@ -310,3 +310,8 @@ def test_no_main_stream_stage_overwrites_what_a_side_stream_stage_still_reads():
     plan = unet._make_plan(2, 64, 64, True)
     fin = [f for k, f in plan.bwd.ops if k == "WGRAD_FINALIZE"]
     assert fin and all(f.get("_flags", 0) & D.FLAG_SIDE for f in fin) and check(plan.bwd) == 0      # no join at all in the U-Net's backward
+    # ... and byte exact, for all three hazard classes and through the tables (tests/stream_order.py; every plan: test_stream_order_cpu.py)
+    from tests import stream_order as SO
+
+    for accept in (True, False):
+        assert not SO.find_conflicts(plan.bwd.ops, plan.const_table, accept)[0]
