@@ -23,15 +23,6 @@
 
 namespace s2k {
 
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-
 struct AttnP {
     const float *qkv, *dout, *o_in;
     float *o, *dqkv, *lse, *delta;
@@ -348,9 +339,6 @@ static int fill_attn(AttnP& p, const int32_t* d, float scale) {
     return S2K_OK;
 }
 
-static bool bad(const void* q) { return q == nullptr || q == reinterpret_cast<const void*>(1); }
-
-
 // one workgroup per (batch, head, group of 4 tiles); LDS = ntiles_buf double-buffered [32*MT][TS] tiles + extra floats
 #define ATTN_LAUNCH_LDS(kernel, p, ntiles_buf, extra, stream)                                                        \
     do {                                                                                                             \
@@ -361,26 +349,28 @@ static bool bad(const void* q) { return q == nullptr || q == reinterpret_cast<co
     } while (0)
 
 int launch_attn_fwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     AttnP p{};
     if (int e = fill_attn(p, op.d, op.f[S2K_ATTN_FWD_F_SCALE])) return e;
-    p.qkv = ref_ptr<const float>(c, op.t[S2K_ATTN_FWD_T_QKV]);
-    p.o = ref_ptr<float>(c, op.t[S2K_ATTN_FWD_T_O]);
-    p.lse = ref_ptr<float>(c, op.t[S2K_ATTN_FWD_T_LSE]);
-    if (bad(p.qkv) || bad(p.o) || bad(p.lse)) { set_error("attn_fwd: missing tensor or null base"); return S2K_EINVAL; }
+    p.qkv = r.ptr<const float>(op.t[S2K_ATTN_FWD_T_QKV]);
+    p.o = r.ptr<float>(op.t[S2K_ATTN_FWD_T_O]);
+    p.lse = r.ptr<float>(op.t[S2K_ATTN_FWD_T_LSE]);
+    if (!p.qkv || !p.o || !p.lse) { set_error("attn_fwd: missing tensor or null base"); return S2K_EINVAL; }
     ATTN_LAUNCH_LDS(attn_fwd_lds_kernel, p, 4, 0, c.stream);
     return S2K_OK;
 }
 
 int launch_attn_bwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     AttnP p{};
     if (int e = fill_attn(p, op.d, op.f[S2K_ATTN_BWD_F_SCALE])) return e;
-    p.qkv = ref_ptr<const float>(c, op.t[S2K_ATTN_BWD_T_QKV]);
-    p.dout = ref_ptr<const float>(c, op.t[S2K_ATTN_BWD_T_DO]);
-    p.dqkv = ref_ptr<float>(c, op.t[S2K_ATTN_BWD_T_DQKV]);
-    p.o_in = ref_ptr<const float>(c, op.t[S2K_ATTN_BWD_T_O]);
-    p.lse = ref_ptr<float>(c, op.t[S2K_ATTN_BWD_T_LSE]);
-    p.delta = ref_ptr<float>(c, op.t[S2K_ATTN_BWD_T_DELTA]);
-    if (bad(p.qkv) || bad(p.dout) || bad(p.dqkv) || bad(p.o_in) || bad(p.lse) || bad(p.delta)) {
+    p.qkv = r.ptr<const float>(op.t[S2K_ATTN_BWD_T_QKV]);
+    p.dout = r.ptr<const float>(op.t[S2K_ATTN_BWD_T_DO]);
+    p.dqkv = r.ptr<float>(op.t[S2K_ATTN_BWD_T_DQKV]);
+    p.o_in = r.ptr<const float>(op.t[S2K_ATTN_BWD_T_O]);
+    p.lse = r.ptr<float>(op.t[S2K_ATTN_BWD_T_LSE]);
+    p.delta = r.ptr<float>(op.t[S2K_ATTN_BWD_T_DELTA]);
+    if (!p.qkv || !p.dout || !p.dqkv || !p.o_in || !p.lse || !p.delta) {
         set_error("attn_bwd: missing tensor or null base"); return S2K_EINVAL;
     }
     ATTN_LAUNCH_LDS(attn_bwd_dq_lds_kernel, p, 4, 0, c.stream);      // also writes delta, which the dK/dV kernel reads

@@ -15,7 +15,7 @@
 // host) - and adds its non-zero cells to HIST with one 64-bit global atomic each when it ends.  The per-temperature sums live in one
 // 64-bit LDS slot per (temperature, thread), are summed per wave and per workgroup, and reach TOTALS as one atomic per workgroup and
 // temperature.  Integer addition commutes: the results are independent of the launch geometry and bit-identical from run to run.
-#include "common.h"
+#include "plain.h"
 
 #include <cmath>
 

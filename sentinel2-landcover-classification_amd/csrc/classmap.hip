@@ -22,7 +22,7 @@
 // WINDOW_BLEND's (csrc/predict.hip): 32-bit LDS bins per workgroup (it counts at most 16 x 62 pixels; several copies of each bin where
 // K is small, so that a wave's adds do not queue on one address), then one 64-bit atomic per non-zero bin; CHANGED is one 64-bit atomic
 // per workgroup.  Integer sums: exact, independent of launch geometry.
-#include "common.h"
+#include "plain.h"
 
 namespace s2k {
 

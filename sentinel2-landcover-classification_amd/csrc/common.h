@@ -346,19 +346,38 @@ struct Ctx {
     hipStream_t stream;
 };
 
+// The one decoder of a tensor reference (base << 56 | byte offset; negative = NULL).  A launcher resolves every tensor of its record
+// through one Refs and asks `absent` once, before it uses any of the pointers: a NULL reference gives nullptr, a reference into a
+// base the caller did not bind gives nullptr and sets `absent`.
+struct Refs {
+    const Ctx& c;
+    bool absent = false;
+    explicit Refs(const Ctx& ctx) : c(ctx) {}
+    static int base_of(int64_t ref) { return (int)(ref >> 56); }
+    template <typename T>
+    T* ptr(int64_t ref) {
+        if (ref < 0) return nullptr;
+        const int base = base_of(ref);
+        if (base >= c.n_bases || c.bases[base] == nullptr) { absent = true; return nullptr; }
+        return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + (ref & ((1ll << 56) - 1)));
+    }
+    // the answer of most launchers to an absent base
+    int fault(const char* who) const { set_error("%s: tensor references a null base", who); return S2K_EFAULT; }
+};
+
 // host side of BnFold: the five tensor refs FSTATS, FGAMMA, FBETA, FRM, FRV (consecutive t slots) + scalars of a stage record
+// (bnv: resolved by the caller, which has already asked its Refs for an absent base)
 inline int fill_bn_fold(BnFold& f, const Ctx& c, const int64_t* t5, int64_t count, int nrep, float eps, float mom, float* bnv,
                         const char* who) {
     f = BnFold{};
     if (t5[0] < 0) return S2K_OK;                       // not folded
+    Refs r(c);
     void* ptr[5];
     for (int i = 0; i < 5; ++i) {
-        const int64_t ref = t5[i];
-        const int base = (int)(ref >> 56);
-        if (ref < 0 || base >= c.n_bases || c.bases[base] == nullptr) { set_error("%s: folded BN_FINALIZE needs FSTATS, FGAMMA, FBETA, FRM, FRV", who); return S2K_EINVAL; }
-        ptr[i] = static_cast<char*>(c.bases[base]) + (ref & ((1ll << 56) - 1));
+        ptr[i] = r.ptr<void>(t5[i]);
+        if (!ptr[i]) { set_error("%s: folded BN_FINALIZE needs FSTATS, FGAMMA, FBETA, FRM, FRV", who); return S2K_EINVAL; }
     }
-    if (count <= 0 || !bnv || bnv == reinterpret_cast<float*>(1)) { set_error("%s: folded BN_FINALIZE needs FCOUNT > 0 and BNV", who); return S2K_EINVAL; }
+    if (count <= 0 || !bnv) { set_error("%s: folded BN_FINALIZE needs FCOUNT > 0 and BNV", who); return S2K_EINVAL; }
     f.stats = static_cast<const double*>(ptr[0]);
     f.gamma = static_cast<const float*>(ptr[1]);
     f.beta = static_cast<const float*>(ptr[2]);

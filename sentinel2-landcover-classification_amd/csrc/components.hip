@@ -29,7 +29,7 @@
 //   RELABEL  every pixel of a small component writes `to` or the class of its donor's root in the INPUT map, everything else is
 //            copied; CHANGED and HIST are counted as s2k_classmap_filter counts them (LDS bins in copies, one 64-bit atomic per bin).
 // Map offsets are 64-bit, offsets inside a map 32-bit.
-#include "common.h"
+#include "plain.h"
 
 namespace s2k {
 

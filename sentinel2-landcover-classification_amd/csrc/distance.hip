@@ -25,7 +25,7 @@
 // workgroup by EDT_ROWS; there is no data-dependent `while`, and therefore no status word.  The worst case of the pruned search is one
 // site in a corner: about W steps per pixel (tools/bench_distance.py times it).
 // Map offsets are 64-bit, offsets inside a map 32-bit.
-#include "common.h"
+#include "plain.h"
 
 namespace s2k {
 

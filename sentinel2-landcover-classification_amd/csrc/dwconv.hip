@@ -1477,17 +1477,6 @@ __global__ void __launch_bounds__(NTHREADS) dwconv_dgrad_s2_kernel(const DwP p) 
 }
 
 // -------------------------------------------------------------------------------------------------
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-
-static bool bad(const void* q) { return q == reinterpret_cast<const void*>(1); }
-
 static int fill_geo(DwP& p, const int32_t* d) {
     p.B = d[0]; p.C = d[1]; p.H = d[2]; p.W = d[3]; p.K = d[4]; p.S = d[5]; p.PT = d[6]; p.PL = d[7];
     p.HO = d[8]; p.WO = d[9]; p.pro = d[10]; p.nrep = 1; p.beta = 0;
@@ -1543,15 +1532,16 @@ static int launch_dw(KernT kern, const DwP& p, size_t lds, hipStream_t st) {
 }
 
 int launch_dwconv_fwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     DwP p{};
     if (int e = fill_geo(p, op.d)) return e;
-    p.x = ref_ptr<const float>(c, op.t[S2K_DWCONV_FWD_T_X]);
-    p.bnv = ref_ptr<const float>(c, op.t[S2K_DWCONV_FWD_T_BNV]);
-    p.w = ref_ptr<const float>(c, op.t[S2K_DWCONV_FWD_T_WT]);
-    p.out = ref_ptr<float>(c, op.t[S2K_DWCONV_FWD_T_Y]);
-    p.stats = ref_ptr<double>(c, op.t[S2K_DWCONV_FWD_T_STATS]);
+    p.x = r.ptr<const float>(op.t[S2K_DWCONV_FWD_T_X]);
+    p.bnv = r.ptr<const float>(op.t[S2K_DWCONV_FWD_T_BNV]);
+    p.w = r.ptr<const float>(op.t[S2K_DWCONV_FWD_T_WT]);
+    p.out = r.ptr<float>(op.t[S2K_DWCONV_FWD_T_Y]);
+    p.stats = r.ptr<double>(op.t[S2K_DWCONV_FWD_T_STATS]);
     if (op.d[S2K_DWCONV_FWD_D_NREP] > 0) p.nrep = op.d[S2K_DWCONV_FWD_D_NREP];
-    if (bad(p.x) || bad(p.bnv) || bad(p.w) || bad(p.out) || bad(p.stats)) { set_error("dwconv_fwd: null base"); return S2K_EFAULT; }
+    if (r.absent) { set_error("dwconv_fwd: null base"); return S2K_EFAULT; }
     if (!p.x || !p.w || !p.out || (p.pro != S2K_PRO_NONE && !p.bnv)) { set_error("dwconv_fwd: missing tensor"); return S2K_EINVAL; }
     if (int e = fill_bn_fold(p.fold, c, &op.t[S2K_DWCONV_FWD_T_FSTATS], op.n[S2K_DWCONV_FWD_N_FCOUNT], op.d[S2K_DWCONV_FWD_D_FNREP],
                              op.f[S2K_DWCONV_FWD_F_FEPS], op.f[S2K_DWCONV_FWD_F_FMOM], const_cast<float*>(p.bnv), "dwconv_fwd")) return e;
@@ -1626,13 +1616,14 @@ int launch_dwconv_fwd(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_dwconv_wgrad(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     DwP p{};
     if (int e = fill_geo(p, op.d)) return e;
-    p.dy = ref_ptr<const float>(c, op.t[S2K_DWCONV_WGRAD_T_DY]);
-    p.x = ref_ptr<const float>(c, op.t[S2K_DWCONV_WGRAD_T_X]);
-    p.bnv = ref_ptr<const float>(c, op.t[S2K_DWCONV_WGRAD_T_BNV]);
-    p.out = ref_ptr<float>(c, op.t[S2K_DWCONV_WGRAD_T_DW]);
-    if (bad(p.x) || bad(p.bnv) || bad(p.dy) || bad(p.out)) { set_error("dwconv_wgrad: null base"); return S2K_EFAULT; }
+    p.dy = r.ptr<const float>(op.t[S2K_DWCONV_WGRAD_T_DY]);
+    p.x = r.ptr<const float>(op.t[S2K_DWCONV_WGRAD_T_X]);
+    p.bnv = r.ptr<const float>(op.t[S2K_DWCONV_WGRAD_T_BNV]);
+    p.out = r.ptr<float>(op.t[S2K_DWCONV_WGRAD_T_DW]);
+    if (r.absent) { set_error("dwconv_wgrad: null base"); return S2K_EFAULT; }
     if (!p.x || !p.dy || !p.out || (p.pro != S2K_PRO_NONE && !p.bnv)) { set_error("dwconv_wgrad: missing tensor"); return S2K_EINVAL; }
     static const int plane_on = tune_int("S2K_DW_PLANE", 1);
     if (plane_on && p.S == 1 && p.H == p.W && (p.W == 8 || p.W == 16 || p.W == 32 || p.W == 64 || (p.W == 128 && p.K == 3)) &&
@@ -1712,17 +1703,18 @@ int launch_dwconv_wgrad(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_dwconv_dgrad(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     DwP p{};
     if (int e = fill_geo(p, op.d)) return e;
     p.beta = op.d[S2K_DWCONV_DGRAD_D_BETA];
     if (op.d[S2K_DWCONV_DGRAD_D_NREP] > 0) p.nrep = op.d[S2K_DWCONV_DGRAD_D_NREP];
-    p.dy = ref_ptr<const float>(c, op.t[S2K_DWCONV_DGRAD_T_DY]);
-    p.w = ref_ptr<const float>(c, op.t[S2K_DWCONV_DGRAD_T_WT]);
-    p.x = ref_ptr<const float>(c, op.t[S2K_DWCONV_DGRAD_T_XRAW]);
-    p.bnv = ref_ptr<const float>(c, op.t[S2K_DWCONV_DGRAD_T_BNV]);
-    p.out = ref_ptr<float>(c, op.t[S2K_DWCONV_DGRAD_T_G]);
-    p.stats = ref_ptr<double>(c, op.t[S2K_DWCONV_DGRAD_T_STATS2]);
-    if (bad(p.x) || bad(p.bnv) || bad(p.dy) || bad(p.out) || bad(p.w) || bad(p.stats)) { set_error("dwconv_dgrad: null base"); return S2K_EFAULT; }
+    p.dy = r.ptr<const float>(op.t[S2K_DWCONV_DGRAD_T_DY]);
+    p.w = r.ptr<const float>(op.t[S2K_DWCONV_DGRAD_T_WT]);
+    p.x = r.ptr<const float>(op.t[S2K_DWCONV_DGRAD_T_XRAW]);
+    p.bnv = r.ptr<const float>(op.t[S2K_DWCONV_DGRAD_T_BNV]);
+    p.out = r.ptr<float>(op.t[S2K_DWCONV_DGRAD_T_G]);
+    p.stats = r.ptr<double>(op.t[S2K_DWCONV_DGRAD_T_STATS2]);
+    if (r.absent) { set_error("dwconv_dgrad: null base"); return S2K_EFAULT; }
     if (!p.dy || !p.w || !p.out || (p.pro != S2K_PRO_NONE && (!p.bnv || !p.x))) { set_error("dwconv_dgrad: missing tensor"); return S2K_EINVAL; }
     if (p.pro == S2K_PRO_NONE) p.stats = nullptr;
     if (p.S == 1) {
@@ -1801,31 +1793,31 @@ int launch_dwconv_dgrad(const S2kOp& op, const Ctx& c) {
 // pattern: kinds, matching tensor references, stride 1, W = H in {8, 16}, K in {3, 5}, train-mode, f32 in place.
 int launch_dw_bwd_chain(const S2kOp* o, const Ctx& c) {
     const S2kOp &a1 = o[0], &wg = o[1], &dg = o[2], &a2 = o[3];
+    Refs r(c);
     DwChainP p{};
-    p.d = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_GP]);
-    p.dy = ref_ptr<float>(c, a1.t[S2K_BN_BWD_APPLY_T_DY]);
-    p.ydw = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_Y]);
-    p.bnv1 = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_BNV]);
-    p.mulbc = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_MULBC]);
-    p.addbc = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_ADDBC]);
-    p.ps = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_PS]);
-    p.gamma1 = ref_ptr<const float>(c, a1.t[S2K_BN_BWD_APPLY_T_GAMMA]);
-    p.dgamma1 = ref_ptr<float>(c, a1.t[S2K_BN_BWD_APPLY_T_DGAMMA]);
-    p.dbeta1 = ref_ptr<float>(c, a1.t[S2K_BN_BWD_APPLY_T_DBETA]);
-    p.x = ref_ptr<const float>(c, dg.t[S2K_DWCONV_DGRAD_T_XRAW]);
-    p.bnv2 = ref_ptr<const float>(c, dg.t[S2K_DWCONV_DGRAD_T_BNV]);
-    p.w = ref_ptr<const float>(c, dg.t[S2K_DWCONV_DGRAD_T_WT]);
-    p.dw = ref_ptr<float>(c, wg.t[S2K_DWCONV_WGRAD_T_DW]);
-    p.g = ref_ptr<float>(c, dg.t[S2K_DWCONV_DGRAD_T_G]);
-    p.gamma2 = ref_ptr<const float>(c, a2.t[S2K_BN_BWD_APPLY_T_GAMMA]);
-    p.dgamma2 = ref_ptr<float>(c, a2.t[S2K_BN_BWD_APPLY_T_DGAMMA]);
-    p.dbeta2 = ref_ptr<float>(c, a2.t[S2K_BN_BWD_APPLY_T_DBETA]);
+    p.d = r.ptr<const float>(a1.t[S2K_BN_BWD_APPLY_T_GP]);
+    p.dy = r.ptr<float>(a1.t[S2K_BN_BWD_APPLY_T_DY]);
+    p.ydw = r.ptr<const float>(a1.t[S2K_BN_BWD_APPLY_T_Y]);
+    p.bnv1 = r.ptr<const float>(a1.t[S2K_BN_BWD_APPLY_T_BNV]);
+    p.mulbc = r.ptr<const float>(a1.t[S2K_BN_BWD_APPLY_T_MULBC]);
+    p.addbc = r.ptr<const float>(a1.t[S2K_BN_BWD_APPLY_T_ADDBC]);
+    p.ps = r.ptr<const float>(a1.t[S2K_BN_BWD_APPLY_T_PS]);
+    p.gamma1 = r.ptr<const float>(a1.t[S2K_BN_BWD_APPLY_T_GAMMA]);
+    p.dgamma1 = r.ptr<float>(a1.t[S2K_BN_BWD_APPLY_T_DGAMMA]);
+    p.dbeta1 = r.ptr<float>(a1.t[S2K_BN_BWD_APPLY_T_DBETA]);
+    p.x = r.ptr<const float>(dg.t[S2K_DWCONV_DGRAD_T_XRAW]);
+    p.bnv2 = r.ptr<const float>(dg.t[S2K_DWCONV_DGRAD_T_BNV]);
+    p.w = r.ptr<const float>(dg.t[S2K_DWCONV_DGRAD_T_WT]);
+    p.dw = r.ptr<float>(wg.t[S2K_DWCONV_WGRAD_T_DW]);
+    p.g = r.ptr<float>(dg.t[S2K_DWCONV_DGRAD_T_G]);
+    p.gamma2 = r.ptr<const float>(a2.t[S2K_BN_BWD_APPLY_T_GAMMA]);
+    p.dgamma2 = r.ptr<float>(a2.t[S2K_BN_BWD_APPLY_T_DGAMMA]);
+    p.dbeta2 = r.ptr<float>(a2.t[S2K_BN_BWD_APPLY_T_DBETA]);
     const void* all[] = {p.d, p.dy, p.ydw, p.bnv1, p.mulbc, p.addbc, p.ps, p.gamma1, p.dgamma1, p.dbeta1, p.x, p.bnv2, p.w, p.dw, p.g, p.gamma2,
                          p.dgamma2, p.dbeta2};
-    for (const void* q : all) {
-        if (bad(q)) { set_error("dw_bwd_chain: null base"); return S2K_EFAULT; }
+    if (r.absent) { set_error("dw_bwd_chain: null base"); return S2K_EFAULT; }
+    for (const void* q : all)
         if (!q) { set_error("dw_bwd_chain: missing tensor"); return S2K_EINVAL; }
-    }
     p.B = dg.d[0]; p.C = dg.d[1];
     const int W = dg.d[3], K = dg.d[4];
     p.inv_count1 = 1.0 / (double)a1.n[S2K_BN_BWD_APPLY_N_COUNT];

@@ -6,26 +6,11 @@
 // Work decomposition: one wave per (plane, chunk) task, float4 accesses when the plane size allows,
 // wave shuffle reductions, one f64 atomic per task for per-channel sums.
 #include "common.h"
+#include "plain.h"
 
 namespace s2k {
 
 constexpr int CHUNK = 4096;   // elements of one (b,c) plane handled by one wave
-
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-static bool bad(const void* q) { return q == reinterpret_cast<const void*>(1); }
-#define CHECK_PTRS(name, ...)                                                                         \
-    do {                                                                                              \
-        const void* _ps[] = {__VA_ARGS__};                                                            \
-        for (const void* _q : _ps)                                                                    \
-            if (bad(_q)) { set_error(name ": tensor references a null base"); return S2K_EFAULT; }    \
-    } while (0)
 
 struct Task {
     int64_t plane;
@@ -64,9 +49,10 @@ __global__ void axpy_kernel(const float* x, float* y, int64_t n) {
 }
 
 int launch_axpy(const S2kOp& op, const Ctx& c) {
-    const float* x = ref_ptr<const float>(c, op.t[S2K_AXPY_T_X]);
-    float* y = ref_ptr<float>(c, op.t[S2K_AXPY_T_Y]);
-    CHECK_PTRS("axpy", x, y);
+    Refs r(c);
+    const float* x = r.ptr<const float>(op.t[S2K_AXPY_T_X]);
+    float* y = r.ptr<float>(op.t[S2K_AXPY_T_Y]);
+    if (r.absent) return r.fault("axpy");
     const int64_t n = op.n[S2K_AXPY_N_COUNT];
     if (!x || !y || n <= 0) { set_error("axpy: bad args"); return S2K_EINVAL; }
     const int blocks = (int)std::min<int64_t>(cdiv64(n, 4 * 256), 2048);
@@ -97,10 +83,11 @@ __global__ void wgrad_finalize_kernel(const int* table, int n_entries, const flo
 }
 
 int launch_wgrad_finalize(const S2kOp& op, const Ctx& c) {
-    const int* table = ref_ptr<const int>(c, op.t[S2K_WGRAD_FINALIZE_T_TABLE]);
-    const float* wgs = ref_ptr<const float>(c, op.t[S2K_WGRAD_FINALIZE_T_WGS]);
-    float* grads = ref_ptr<float>(c, op.t[S2K_WGRAD_FINALIZE_T_GRADS]);
-    CHECK_PTRS("wgrad_finalize", table, wgs, grads);
+    Refs r(c);
+    const int* table = r.ptr<const int>(op.t[S2K_WGRAD_FINALIZE_T_TABLE]);
+    const float* wgs = r.ptr<const float>(op.t[S2K_WGRAD_FINALIZE_T_WGS]);
+    float* grads = r.ptr<float>(op.t[S2K_WGRAD_FINALIZE_T_GRADS]);
+    if (r.absent) return r.fault("wgrad_finalize");
     const int64_t total = op.n[S2K_WGRAD_FINALIZE_N_TOTAL];
     const int n = op.d[S2K_WGRAD_FINALIZE_D_N_ENTRIES];
     if (!table || !wgs || !grads || n <= 0 || total <= 0 || total > 0x7fffffff) { set_error("wgrad_finalize: bad args"); return S2K_EINVAL; }
@@ -238,10 +225,11 @@ __global__ void __launch_bounds__(NTHREADS) weight_pack_q4_kernel(const int* tab
 }
 
 int launch_weight_pack(const S2kOp& op, const Ctx& c) {
-    const int* table = ref_ptr<const int>(c, op.t[S2K_WEIGHT_PACK_T_TABLE]);
-    const float* src = ref_ptr<const float>(c, op.t[S2K_WEIGHT_PACK_T_SRC]);
-    float* dst = ref_ptr<float>(c, op.t[S2K_WEIGHT_PACK_T_DST]);
-    CHECK_PTRS("weight_pack", table, src, dst);
+    Refs r(c);
+    const int* table = r.ptr<const int>(op.t[S2K_WEIGHT_PACK_T_TABLE]);
+    const float* src = r.ptr<const float>(op.t[S2K_WEIGHT_PACK_T_SRC]);
+    float* dst = r.ptr<float>(op.t[S2K_WEIGHT_PACK_T_DST]);
+    if (r.absent) return r.fault("weight_pack");
     const int64_t total = op.n[S2K_WEIGHT_PACK_N_TOTAL];
     const int n = op.d[S2K_WEIGHT_PACK_D_N_ENTRIES];
     if (!table || !src || !dst || n <= 0 || total <= 0 || (total & 4095) || (total >> 12) > 0x7fffffff) {
@@ -302,13 +290,14 @@ __global__ void bn_finalize_kernel(const double* stats, const float* gamma, cons
 }
 
 int launch_bn_finalize(const S2kOp& op, const Ctx& c) {
-    const double* stats = ref_ptr<const double>(c, op.t[S2K_BN_FINALIZE_T_STATS]);
-    const float* gamma = ref_ptr<const float>(c, op.t[S2K_BN_FINALIZE_T_GAMMA]);
-    const float* beta = ref_ptr<const float>(c, op.t[S2K_BN_FINALIZE_T_BETA]);
-    float* rm = ref_ptr<float>(c, op.t[S2K_BN_FINALIZE_T_RM]);
-    float* rv = ref_ptr<float>(c, op.t[S2K_BN_FINALIZE_T_RV]);
-    float* bnv = ref_ptr<float>(c, op.t[S2K_BN_FINALIZE_T_BNV]);
-    CHECK_PTRS("bn_finalize", stats, gamma, beta, rm, rv, bnv);
+    Refs r(c);
+    const double* stats = r.ptr<const double>(op.t[S2K_BN_FINALIZE_T_STATS]);
+    const float* gamma = r.ptr<const float>(op.t[S2K_BN_FINALIZE_T_GAMMA]);
+    const float* beta = r.ptr<const float>(op.t[S2K_BN_FINALIZE_T_BETA]);
+    float* rm = r.ptr<float>(op.t[S2K_BN_FINALIZE_T_RM]);
+    float* rv = r.ptr<float>(op.t[S2K_BN_FINALIZE_T_RV]);
+    float* bnv = r.ptr<float>(op.t[S2K_BN_FINALIZE_T_BNV]);
+    if (r.absent) return r.fault("bn_finalize");
     const int C = op.d[S2K_BN_FINALIZE_D_C], train = op.d[S2K_BN_FINALIZE_D_TRAIN];
     if (!gamma || !beta || !rm || !rv || !bnv || C <= 0 || (train && !stats)) { set_error("bn_finalize: bad args"); return S2K_EINVAL; }
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), 0, c.stream, stats, gamma, beta, rm, rv, bnv, C,
@@ -452,10 +441,11 @@ static int launch_plane_reduce(const float* g, const float* y, const float* bnv,
 }
 
 int launch_se_pool(const S2kOp& op, const Ctx& c) {
-    const float* y = ref_ptr<const float>(c, op.t[S2K_SE_POOL_T_Y]);
-    const float* bnv = ref_ptr<const float>(c, op.t[S2K_SE_POOL_T_BNV]);
-    float* pool = ref_ptr<float>(c, op.t[S2K_SE_POOL_T_POOL]);
-    CHECK_PTRS("se_pool", y, bnv, pool);
+    Refs r(c);
+    const float* y = r.ptr<const float>(op.t[S2K_SE_POOL_T_Y]);
+    const float* bnv = r.ptr<const float>(op.t[S2K_SE_POOL_T_BNV]);
+    float* pool = r.ptr<float>(op.t[S2K_SE_POOL_T_POOL]);
+    if (r.absent) return r.fault("se_pool");
     const int pro = op.d[S2K_SE_POOL_D_PRO];
     if (!y || !pool || (pro && !bnv)) { set_error("se_pool: bad args"); return S2K_EINVAL; }
     BnFold fold;
@@ -482,11 +472,12 @@ int launch_se_pool(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_se_bwd_reduce(const S2kOp& op, const Ctx& c) {
-    const float* g = ref_ptr<const float>(c, op.t[S2K_SE_BWD_REDUCE_T_G]);
-    const float* y = ref_ptr<const float>(c, op.t[S2K_SE_BWD_REDUCE_T_Y]);
-    const float* bnv = ref_ptr<const float>(c, op.t[S2K_SE_BWD_REDUCE_T_BNV]);
-    float* out = ref_ptr<float>(c, op.t[S2K_SE_BWD_REDUCE_T_DGATE]);
-    CHECK_PTRS("se_bwd_reduce", g, y, bnv, out);
+    Refs r(c);
+    const float* g = r.ptr<const float>(op.t[S2K_SE_BWD_REDUCE_T_G]);
+    const float* y = r.ptr<const float>(op.t[S2K_SE_BWD_REDUCE_T_Y]);
+    const float* bnv = r.ptr<const float>(op.t[S2K_SE_BWD_REDUCE_T_BNV]);
+    float* out = r.ptr<float>(op.t[S2K_SE_BWD_REDUCE_T_DGATE]);
+    if (r.absent) return r.fault("se_bwd_reduce");
     const int pro = op.d[S2K_SE_BWD_REDUCE_D_PRO];
     if (!g || !y || !out || (pro && !bnv)) { set_error("se_bwd_reduce: bad args"); return S2K_EINVAL; }
     return launch_plane_reduce<1>(g, y, bnv, out, op.d[S2K_SE_BWD_REDUCE_D_B], op.d[S2K_SE_BWD_REDUCE_D_C],
@@ -641,12 +632,13 @@ __global__ void __launch_bounds__(NTHREADS) se_bn_sums_small_kernel(const float*
 }
 
 int launch_se_bn_sums(const S2kOp& op, const Ctx& c) {
-    const float* g = ref_ptr<const float>(c, op.t[S2K_SE_BN_SUMS_T_G]);
-    const float* y = ref_ptr<const float>(c, op.t[S2K_SE_BN_SUMS_T_Y]);
-    const float* bnv = ref_ptr<const float>(c, op.t[S2K_SE_BN_SUMS_T_BNV]);
-    float* dgate = ref_ptr<float>(c, op.t[S2K_SE_BN_SUMS_T_DGATE]);
-    float* ps = ref_ptr<float>(c, op.t[S2K_SE_BN_SUMS_T_PS]);
-    CHECK_PTRS("se_bn_sums", g, y, bnv, dgate, ps);
+    Refs r(c);
+    const float* g = r.ptr<const float>(op.t[S2K_SE_BN_SUMS_T_G]);
+    const float* y = r.ptr<const float>(op.t[S2K_SE_BN_SUMS_T_Y]);
+    const float* bnv = r.ptr<const float>(op.t[S2K_SE_BN_SUMS_T_BNV]);
+    float* dgate = r.ptr<float>(op.t[S2K_SE_BN_SUMS_T_DGATE]);
+    float* ps = r.ptr<float>(op.t[S2K_SE_BN_SUMS_T_PS]);
+    if (r.absent) return r.fault("se_bn_sums");
     const int B = op.d[S2K_SE_BN_SUMS_D_B], C = op.d[S2K_SE_BN_SUMS_D_C], HW = op.d[S2K_SE_BN_SUMS_D_HW];
     if (!g || !y || !bnv || !dgate || !ps || B <= 0 || C <= 0 || HW <= 0 || op.d[S2K_SE_BN_SUMS_D_ACT] != S2K_PRO_SILU) {
         set_error("se_bn_sums: bad args (SiLU only)"); return S2K_EINVAL;
@@ -694,11 +686,12 @@ __global__ void __launch_bounds__(NTHREADS) se_bn_combine_kernel(const float* ps
 }
 
 int launch_se_bn_combine(const S2kOp& op, const Ctx& c) {
-    const float* ps = ref_ptr<const float>(c, op.t[S2K_SE_BN_COMBINE_T_PS]);
-    const float* mulbc = ref_ptr<const float>(c, op.t[S2K_SE_BN_COMBINE_T_MULBC]);
-    const float* addbc = ref_ptr<const float>(c, op.t[S2K_SE_BN_COMBINE_T_ADDBC]);
-    double* st2 = ref_ptr<double>(c, op.t[S2K_SE_BN_COMBINE_T_STATS2]);
-    CHECK_PTRS("se_bn_combine", ps, mulbc, addbc, st2);
+    Refs r(c);
+    const float* ps = r.ptr<const float>(op.t[S2K_SE_BN_COMBINE_T_PS]);
+    const float* mulbc = r.ptr<const float>(op.t[S2K_SE_BN_COMBINE_T_MULBC]);
+    const float* addbc = r.ptr<const float>(op.t[S2K_SE_BN_COMBINE_T_ADDBC]);
+    double* st2 = r.ptr<double>(op.t[S2K_SE_BN_COMBINE_T_STATS2]);
+    if (r.absent) return r.fault("se_bn_combine");
     const int B = op.d[S2K_SE_BN_COMBINE_D_B], C = op.d[S2K_SE_BN_COMBINE_D_C];
     if (!ps || !st2 || B <= 0 || C <= 0) { set_error("se_bn_combine: bad args"); return S2K_EINVAL; }
     hipLaunchKernelGGL(se_bn_combine_kernel, dim3(cdiv(C, 4)), dim3(NTHREADS), 0, c.stream, ps, mulbc, addbc, st2, B, C, op.f[S2K_SE_BN_COMBINE_F_ADDSCALE]);
@@ -736,9 +729,10 @@ __global__ void __launch_bounds__(NTHREADS) channel_sum_rows_kernel(const float*
 }
 
 int launch_channel_sum(const S2kOp& op, const Ctx& c) {
-    const float* g = ref_ptr<const float>(c, op.t[S2K_CHANNEL_SUM_T_G]);
-    float* out = ref_ptr<float>(c, op.t[S2K_CHANNEL_SUM_T_OUT]);
-    CHECK_PTRS("channel_sum", g, out);
+    Refs r(c);
+    const float* g = r.ptr<const float>(op.t[S2K_CHANNEL_SUM_T_G]);
+    float* out = r.ptr<float>(op.t[S2K_CHANNEL_SUM_T_OUT]);
+    if (r.absent) return r.fault("channel_sum");
     if (!g || !out) { set_error("channel_sum: bad args"); return S2K_EINVAL; }
     const int B = op.d[S2K_CHANNEL_SUM_D_B], C = op.d[S2K_CHANNEL_SUM_D_C], HW = op.d[S2K_CHANNEL_SUM_D_HW];
     if (B > 0 && C >= 256 && HW > 0 && HW <= 512) {
@@ -794,14 +788,15 @@ __global__ void __launch_bounds__(NTHREADS) se_fc2_kernel(const float* hpre, con
 }
 
 int launch_se_fc(const S2kOp& op, const Ctx& c) {
-    const float* pool = ref_ptr<const float>(c, op.t[S2K_SE_FC_T_POOL]);
-    const float* w1 = ref_ptr<const float>(c, op.t[S2K_SE_FC_T_W1]);
-    const float* b1 = ref_ptr<const float>(c, op.t[S2K_SE_FC_T_B1]);
-    const float* w2 = ref_ptr<const float>(c, op.t[S2K_SE_FC_T_W2]);
-    const float* b2 = ref_ptr<const float>(c, op.t[S2K_SE_FC_T_B2]);
-    float* hpre = ref_ptr<float>(c, op.t[S2K_SE_FC_T_HPRE]);
-    float* gate = ref_ptr<float>(c, op.t[S2K_SE_FC_T_GATE]);
-    CHECK_PTRS("se_fc", pool, w1, b1, w2, b2, hpre, gate);
+    Refs r(c);
+    const float* pool = r.ptr<const float>(op.t[S2K_SE_FC_T_POOL]);
+    const float* w1 = r.ptr<const float>(op.t[S2K_SE_FC_T_W1]);
+    const float* b1 = r.ptr<const float>(op.t[S2K_SE_FC_T_B1]);
+    const float* w2 = r.ptr<const float>(op.t[S2K_SE_FC_T_W2]);
+    const float* b2 = r.ptr<const float>(op.t[S2K_SE_FC_T_B2]);
+    float* hpre = r.ptr<float>(op.t[S2K_SE_FC_T_HPRE]);
+    float* gate = r.ptr<float>(op.t[S2K_SE_FC_T_GATE]);
+    if (r.absent) return r.fault("se_fc");
     const int B = op.d[S2K_SE_FC_D_B], C = op.d[S2K_SE_FC_D_C], Q = op.d[S2K_SE_FC_D_CSQ];
     if (!pool || !w1 || !b1 || !w2 || !b2 || !hpre || !gate || B <= 0 || C <= 0 || Q <= 0 || Q > 8192 || B > 65535) {
         set_error("se_fc: bad args"); return S2K_EINVAL;
@@ -1084,19 +1079,20 @@ __global__ void __launch_bounds__(1024) se_fc_bwd_small_kernel(float* dgate, con
 }
 
 int launch_se_fc_bwd(const S2kOp& op, const Ctx& c) {
-    float* dgate = ref_ptr<float>(c, op.t[S2K_SE_FC_BWD_T_DGATE]);
-    const float* gate = ref_ptr<const float>(c, op.t[S2K_SE_FC_BWD_T_GATE]);
-    float* hpre = ref_ptr<float>(c, op.t[S2K_SE_FC_BWD_T_HPRE]);
-    const float* pool = ref_ptr<const float>(c, op.t[S2K_SE_FC_BWD_T_POOL]);
-    const float* w1 = ref_ptr<const float>(c, op.t[S2K_SE_FC_BWD_T_W1]);
-    const float* w2 = ref_ptr<const float>(c, op.t[S2K_SE_FC_BWD_T_W2]);
-    float* dw1 = ref_ptr<float>(c, op.t[S2K_SE_FC_BWD_T_DW1]);
-    float* db1 = ref_ptr<float>(c, op.t[S2K_SE_FC_BWD_T_DB1]);
-    float* dw2 = ref_ptr<float>(c, op.t[S2K_SE_FC_BWD_T_DW2]);
-    float* db2 = ref_ptr<float>(c, op.t[S2K_SE_FC_BWD_T_DB2]);
-    float* dpool = ref_ptr<float>(c, op.t[S2K_SE_FC_BWD_T_DPOOL]);
-    float* hs = ref_ptr<float>(c, op.t[S2K_SE_FC_BWD_T_HS]);
-    CHECK_PTRS("se_fc_bwd", dgate, gate, hpre, pool, w1, w2, dw1, db1, dw2, db2, dpool, hs);
+    Refs r(c);
+    float* dgate = r.ptr<float>(op.t[S2K_SE_FC_BWD_T_DGATE]);
+    const float* gate = r.ptr<const float>(op.t[S2K_SE_FC_BWD_T_GATE]);
+    float* hpre = r.ptr<float>(op.t[S2K_SE_FC_BWD_T_HPRE]);
+    const float* pool = r.ptr<const float>(op.t[S2K_SE_FC_BWD_T_POOL]);
+    const float* w1 = r.ptr<const float>(op.t[S2K_SE_FC_BWD_T_W1]);
+    const float* w2 = r.ptr<const float>(op.t[S2K_SE_FC_BWD_T_W2]);
+    float* dw1 = r.ptr<float>(op.t[S2K_SE_FC_BWD_T_DW1]);
+    float* db1 = r.ptr<float>(op.t[S2K_SE_FC_BWD_T_DB1]);
+    float* dw2 = r.ptr<float>(op.t[S2K_SE_FC_BWD_T_DW2]);
+    float* db2 = r.ptr<float>(op.t[S2K_SE_FC_BWD_T_DB2]);
+    float* dpool = r.ptr<float>(op.t[S2K_SE_FC_BWD_T_DPOOL]);
+    float* hs = r.ptr<float>(op.t[S2K_SE_FC_BWD_T_HS]);
+    if (r.absent) return r.fault("se_fc_bwd");
     const int B = op.d[S2K_SE_FC_BWD_D_B], C = op.d[S2K_SE_FC_BWD_D_C], Q = op.d[S2K_SE_FC_BWD_D_CSQ];
     const bool params = dw1 || db1 || dw2 || db2;        // none: SE_FC_WGRAD computes them (possibly on the side stream)
     if (!dgate || !gate || !hpre || !pool || !w1 || !w2 || !dpool || !hs || B <= 0 || (params && (!dw1 || !db1 || !dw2 || !db2))) {
@@ -1120,15 +1116,16 @@ int launch_se_fc_bwd(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_se_fc_wgrad(const S2kOp& op, const Ctx& c) {
-    const float* dgp = ref_ptr<const float>(c, op.t[S2K_SE_FC_WGRAD_T_DGP]);
-    const float* hs = ref_ptr<const float>(c, op.t[S2K_SE_FC_WGRAD_T_HS]);
-    const float* dhp = ref_ptr<const float>(c, op.t[S2K_SE_FC_WGRAD_T_DHP]);
-    const float* pool = ref_ptr<const float>(c, op.t[S2K_SE_FC_WGRAD_T_POOL]);
-    float* dw1 = ref_ptr<float>(c, op.t[S2K_SE_FC_WGRAD_T_DW1]);
-    float* db1 = ref_ptr<float>(c, op.t[S2K_SE_FC_WGRAD_T_DB1]);
-    float* dw2 = ref_ptr<float>(c, op.t[S2K_SE_FC_WGRAD_T_DW2]);
-    float* db2 = ref_ptr<float>(c, op.t[S2K_SE_FC_WGRAD_T_DB2]);
-    CHECK_PTRS("se_fc_wgrad", dgp, hs, dhp, pool, dw1, db1, dw2, db2);
+    Refs r(c);
+    const float* dgp = r.ptr<const float>(op.t[S2K_SE_FC_WGRAD_T_DGP]);
+    const float* hs = r.ptr<const float>(op.t[S2K_SE_FC_WGRAD_T_HS]);
+    const float* dhp = r.ptr<const float>(op.t[S2K_SE_FC_WGRAD_T_DHP]);
+    const float* pool = r.ptr<const float>(op.t[S2K_SE_FC_WGRAD_T_POOL]);
+    float* dw1 = r.ptr<float>(op.t[S2K_SE_FC_WGRAD_T_DW1]);
+    float* db1 = r.ptr<float>(op.t[S2K_SE_FC_WGRAD_T_DB1]);
+    float* dw2 = r.ptr<float>(op.t[S2K_SE_FC_WGRAD_T_DW2]);
+    float* db2 = r.ptr<float>(op.t[S2K_SE_FC_WGRAD_T_DB2]);
+    if (r.absent) return r.fault("se_fc_wgrad");
     const int B = op.d[S2K_SE_FC_WGRAD_D_B], C = op.d[S2K_SE_FC_WGRAD_D_C], Q = op.d[S2K_SE_FC_WGRAD_D_CSQ];
     if (!dgp || !hs || !dhp || !pool || !dw1 || !db1 || !dw2 || !db2 || B <= 0 || C <= 0 || Q <= 0) { set_error("se_fc_wgrad: bad args"); return S2K_EINVAL; }
     launch_se_fc_param_grads(dgp, hs, dhp, pool, dw1, db1, dw2, db2, B, C, Q, c.stream);
@@ -1190,15 +1187,16 @@ __global__ void __launch_bounds__(NTHREADS) bn_bwd_reduce_kernel(const float* g,
 }
 
 int launch_bn_bwd_reduce(const S2kOp& op, const Ctx& c) {
-    const float* g = ref_ptr<const float>(c, op.t[S2K_BN_BWD_REDUCE_T_G]);
-    const float* y = ref_ptr<const float>(c, op.t[S2K_BN_BWD_REDUCE_T_Y]);
-    const float* bnv = ref_ptr<const float>(c, op.t[S2K_BN_BWD_REDUCE_T_BNV]);
-    const float* mulbc = ref_ptr<const float>(c, op.t[S2K_BN_BWD_REDUCE_T_MULBC]);
-    const float* addbc = ref_ptr<const float>(c, op.t[S2K_BN_BWD_REDUCE_T_ADDBC]);
-    const float* noise = ref_ptr<const float>(c, op.t[S2K_BN_BWD_REDUCE_T_NOISE]);
-    float* gout = ref_ptr<float>(c, op.t[S2K_BN_BWD_REDUCE_T_GOUT]);
-    double* st2 = ref_ptr<double>(c, op.t[S2K_BN_BWD_REDUCE_T_STATS2]);
-    CHECK_PTRS("bn_bwd_reduce", g, y, bnv, mulbc, addbc, noise, gout, st2);
+    Refs r(c);
+    const float* g = r.ptr<const float>(op.t[S2K_BN_BWD_REDUCE_T_G]);
+    const float* y = r.ptr<const float>(op.t[S2K_BN_BWD_REDUCE_T_Y]);
+    const float* bnv = r.ptr<const float>(op.t[S2K_BN_BWD_REDUCE_T_BNV]);
+    const float* mulbc = r.ptr<const float>(op.t[S2K_BN_BWD_REDUCE_T_MULBC]);
+    const float* addbc = r.ptr<const float>(op.t[S2K_BN_BWD_REDUCE_T_ADDBC]);
+    const float* noise = r.ptr<const float>(op.t[S2K_BN_BWD_REDUCE_T_NOISE]);
+    float* gout = r.ptr<float>(op.t[S2K_BN_BWD_REDUCE_T_GOUT]);
+    double* st2 = r.ptr<double>(op.t[S2K_BN_BWD_REDUCE_T_STATS2]);
+    if (r.absent) return r.fault("bn_bwd_reduce");
     const int B = op.d[S2K_BN_BWD_REDUCE_D_B], C = op.d[S2K_BN_BWD_REDUCE_D_C], HW = op.d[S2K_BN_BWD_REDUCE_D_HW];
     if (!g || !y || !bnv || !gout || !st2 || B <= 0 || C <= 0 || HW <= 0) { set_error("bn_bwd_reduce: bad args"); return S2K_EINVAL; }
     const int64_t nplanes = (int64_t)B * C;
@@ -1234,13 +1232,14 @@ __global__ void bn_bwd_finalize_kernel(const double* st2, const float* gamma, co
 }
 
 int launch_bn_bwd_finalize(const S2kOp& op, const Ctx& c) {
-    const double* st2 = ref_ptr<const double>(c, op.t[S2K_BN_BWD_FINALIZE_T_STATS2]);
-    const float* gamma = ref_ptr<const float>(c, op.t[S2K_BN_BWD_FINALIZE_T_GAMMA]);
-    const float* bnv = ref_ptr<const float>(c, op.t[S2K_BN_BWD_FINALIZE_T_BNV]);
-    float* dgamma = ref_ptr<float>(c, op.t[S2K_BN_BWD_FINALIZE_T_DGAMMA]);
-    float* dbeta = ref_ptr<float>(c, op.t[S2K_BN_BWD_FINALIZE_T_DBETA]);
-    float* coef = ref_ptr<float>(c, op.t[S2K_BN_BWD_FINALIZE_T_COEF]);
-    CHECK_PTRS("bn_bwd_finalize", st2, gamma, bnv, dgamma, dbeta, coef);
+    Refs r(c);
+    const double* st2 = r.ptr<const double>(op.t[S2K_BN_BWD_FINALIZE_T_STATS2]);
+    const float* gamma = r.ptr<const float>(op.t[S2K_BN_BWD_FINALIZE_T_GAMMA]);
+    const float* bnv = r.ptr<const float>(op.t[S2K_BN_BWD_FINALIZE_T_BNV]);
+    float* dgamma = r.ptr<float>(op.t[S2K_BN_BWD_FINALIZE_T_DGAMMA]);
+    float* dbeta = r.ptr<float>(op.t[S2K_BN_BWD_FINALIZE_T_DBETA]);
+    float* coef = r.ptr<float>(op.t[S2K_BN_BWD_FINALIZE_T_COEF]);
+    if (r.absent) return r.fault("bn_bwd_finalize");
     const int C = op.d[S2K_BN_BWD_FINALIZE_D_C];
     if (!st2 || !gamma || !bnv || !dgamma || !dbeta || !coef || C <= 0) { set_error("bn_bwd_finalize: bad args"); return S2K_EINVAL; }
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, 4)), dim3(256), 0, c.stream, st2, gamma, bnv, dgamma, dbeta, coef, C,
@@ -1453,20 +1452,21 @@ static void launch_plane_map(const float* a, const float* y, const float* bnv, c
 }
 
 int launch_bn_bwd_apply(const S2kOp& op, const Ctx& c) {
-    const float* gp = ref_ptr<const float>(c, op.t[S2K_BN_BWD_APPLY_T_GP]);
-    const float* y = ref_ptr<const float>(c, op.t[S2K_BN_BWD_APPLY_T_Y]);
-    const float* bnv = ref_ptr<const float>(c, op.t[S2K_BN_BWD_APPLY_T_BNV]);
-    const float* coef = ref_ptr<const float>(c, op.t[S2K_BN_BWD_APPLY_T_COEF]);
-    float* dy = ref_ptr<float>(c, op.t[S2K_BN_BWD_APPLY_T_DY]);
+    Refs r(c);
+    const float* gp = r.ptr<const float>(op.t[S2K_BN_BWD_APPLY_T_GP]);
+    const float* y = r.ptr<const float>(op.t[S2K_BN_BWD_APPLY_T_Y]);
+    const float* bnv = r.ptr<const float>(op.t[S2K_BN_BWD_APPLY_T_BNV]);
+    const float* coef = r.ptr<const float>(op.t[S2K_BN_BWD_APPLY_T_COEF]);
+    float* dy = r.ptr<float>(op.t[S2K_BN_BWD_APPLY_T_DY]);
     BnFuse fz{};
-    fz.st2 = ref_ptr<const double>(c, op.t[S2K_BN_BWD_APPLY_T_STATS2]);
-    fz.gamma = ref_ptr<const float>(c, op.t[S2K_BN_BWD_APPLY_T_GAMMA]);
-    fz.dgamma = ref_ptr<float>(c, op.t[S2K_BN_BWD_APPLY_T_DGAMMA]);
-    fz.dbeta = ref_ptr<float>(c, op.t[S2K_BN_BWD_APPLY_T_DBETA]);
+    fz.st2 = r.ptr<const double>(op.t[S2K_BN_BWD_APPLY_T_STATS2]);
+    fz.gamma = r.ptr<const float>(op.t[S2K_BN_BWD_APPLY_T_GAMMA]);
+    fz.dgamma = r.ptr<float>(op.t[S2K_BN_BWD_APPLY_T_DGAMMA]);
+    fz.dbeta = r.ptr<float>(op.t[S2K_BN_BWD_APPLY_T_DBETA]);
     const double count = (double)op.n[S2K_BN_BWD_APPLY_N_COUNT];
     fz.inv_count = (count > 0 && !op.d[S2K_BN_BWD_APPLY_D_EVAL]) ? 1.0 / count : 0.0;   // EVAL: frozen statistics, Bq = Cq = 0
     fz.nrep = op.d[S2K_BN_BWD_APPLY_D_NREP] > 0 ? op.d[S2K_BN_BWD_APPLY_D_NREP] : 1;
-    CHECK_PTRS("bn_bwd_apply", gp, y, bnv, coef, dy, fz.st2, fz.gamma, fz.dgamma, fz.dbeta);
+    if (r.absent) return r.fault("bn_bwd_apply");
     if (!gp || !y || !bnv || !dy) { set_error("bn_bwd_apply: bad args"); return S2K_EINVAL; }
     const int B = op.d[S2K_BN_BWD_APPLY_D_B], C = op.d[S2K_BN_BWD_APPLY_D_C], HW = op.d[S2K_BN_BWD_APPLY_D_HW];
     if (coef) {
@@ -1475,13 +1475,14 @@ int launch_bn_bwd_apply(const S2kOp& op, const Ctx& c) {
         return S2K_OK;
     }
     // no COEF table: the BN_BWD_FINALIZE arithmetic is done here (one launch less per BatchNorm)
-    fz.ps = ref_ptr<const float>(c, op.t[S2K_BN_BWD_APPLY_T_PS]);
+    fz.ps = r.ptr<const float>(op.t[S2K_BN_BWD_APPLY_T_PS]);
     fz.B = B;
-    if ((!fz.st2 && !fz.ps) || !fz.gamma || !fz.dgamma || !fz.dbeta || count <= 0) { set_error("bn_bwd_apply: fused form needs STATS2 (or PS), GAMMA, DGAMMA, DBETA, COUNT"); return S2K_EINVAL; }
-    fz.mulbc = ref_ptr<const float>(c, op.t[S2K_BN_BWD_APPLY_T_MULBC]);
-    fz.addbc = ref_ptr<const float>(c, op.t[S2K_BN_BWD_APPLY_T_ADDBC]);
+    // (PS given but in an absent base is answered below, with MULBC / ADDBC)
+    if ((!fz.st2 && op.t[S2K_BN_BWD_APPLY_T_PS] < 0) || !fz.gamma || !fz.dgamma || !fz.dbeta || count <= 0) { set_error("bn_bwd_apply: fused form needs STATS2 (or PS), GAMMA, DGAMMA, DBETA, COUNT"); return S2K_EINVAL; }
+    fz.mulbc = r.ptr<const float>(op.t[S2K_BN_BWD_APPLY_T_MULBC]);
+    fz.addbc = r.ptr<const float>(op.t[S2K_BN_BWD_APPLY_T_ADDBC]);
     fz.addscale = op.f[S2K_BN_BWD_APPLY_F_ADDSCALE];
-    CHECK_PTRS("bn_bwd_apply", fz.mulbc, fz.addbc, fz.ps);
+    if (r.absent) return r.fault("bn_bwd_apply");
     if (fz.ps && op.d[S2K_BN_BWD_APPLY_D_ACT] != S2K_PRO_SILU) { set_error("bn_bwd_apply: PS belongs to the recomputing (SiLU) form"); return S2K_EINVAL; }
     const bool out16 = op.d[S2K_BN_BWD_APPLY_D_OUT_BF16] != 0;
     if (out16 && (op.d[S2K_BN_BWD_APPLY_D_ACT] != S2K_PRO_NONE || fz.mulbc || fz.addbc || (HW & 3) || dy == gp)) {
@@ -1507,12 +1508,13 @@ int launch_bn_bwd_apply(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_bn_residual(const S2kOp& op, const Ctx& c) {
-    const float* y = ref_ptr<const float>(c, op.t[S2K_BN_RESIDUAL_T_Y]);
-    const float* bnv = ref_ptr<const float>(c, op.t[S2K_BN_RESIDUAL_T_BNV]);
-    const float* ident = ref_ptr<const float>(c, op.t[S2K_BN_RESIDUAL_T_IDENT]);
-    const float* noise = ref_ptr<const float>(c, op.t[S2K_BN_RESIDUAL_T_NOISE]);
-    float* xout = ref_ptr<float>(c, op.t[S2K_BN_RESIDUAL_T_XOUT]);
-    CHECK_PTRS("bn_residual", y, bnv, ident, noise, xout);
+    Refs r(c);
+    const float* y = r.ptr<const float>(op.t[S2K_BN_RESIDUAL_T_Y]);
+    const float* bnv = r.ptr<const float>(op.t[S2K_BN_RESIDUAL_T_BNV]);
+    const float* ident = r.ptr<const float>(op.t[S2K_BN_RESIDUAL_T_IDENT]);
+    const float* noise = r.ptr<const float>(op.t[S2K_BN_RESIDUAL_T_NOISE]);
+    float* xout = r.ptr<float>(op.t[S2K_BN_RESIDUAL_T_XOUT]);
+    if (r.absent) return r.fault("bn_residual");
     if (!y || !bnv || !xout) { set_error("bn_residual: bad args"); return S2K_EINVAL; }
     BnFold fold;
     if (int e = fill_bn_fold(fold, c, &op.t[S2K_BN_RESIDUAL_T_FSTATS], op.n[S2K_BN_RESIDUAL_N_FCOUNT], op.d[S2K_BN_RESIDUAL_D_FNREP],
@@ -1564,9 +1566,10 @@ __global__ void space_to_depth_scalar_kernel(const float* x, float* y, int C, in
 }
 
 int launch_space_to_depth(const S2kOp& op, const Ctx& c) {
-    const float* x = ref_ptr<const float>(c, op.t[S2K_SPACE_TO_DEPTH_T_X]);
-    float* y = ref_ptr<float>(c, op.t[S2K_SPACE_TO_DEPTH_T_Y]);
-    CHECK_PTRS("space_to_depth", x, y);
+    Refs r(c);
+    const float* x = r.ptr<const float>(op.t[S2K_SPACE_TO_DEPTH_T_X]);
+    float* y = r.ptr<float>(op.t[S2K_SPACE_TO_DEPTH_T_Y]);
+    if (r.absent) return r.fault("space_to_depth");
     const int B = op.d[S2K_SPACE_TO_DEPTH_D_B], C = op.d[S2K_SPACE_TO_DEPTH_D_C], H = op.d[S2K_SPACE_TO_DEPTH_D_H], W = op.d[S2K_SPACE_TO_DEPTH_D_W];
     if (!x || !y || B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("space_to_depth: bad args"); return S2K_EINVAL; }
     if ((W & 3) == 0) {
@@ -1613,9 +1616,10 @@ __global__ void __launch_bounds__(NTHREADS) im2col_kernel(const float* x, float*
 }
 
 int launch_im2col(const S2kOp& op, const Ctx& c) {
-    const float* x = ref_ptr<const float>(c, op.t[S2K_IM2COL_T_X]);
-    float* y = ref_ptr<float>(c, op.t[S2K_IM2COL_T_Y]);
-    CHECK_PTRS("im2col", x, y);
+    Refs r(c);
+    const float* x = r.ptr<const float>(op.t[S2K_IM2COL_T_X]);
+    float* y = r.ptr<float>(op.t[S2K_IM2COL_T_Y]);
+    if (r.absent) return r.fault("im2col");
     const int32_t* d = op.d;
     const int B = d[S2K_IM2COL_D_B], C = d[S2K_IM2COL_D_C], H = d[S2K_IM2COL_D_H], W = d[S2K_IM2COL_D_W], KH = d[S2K_IM2COL_D_KH], KW = d[S2K_IM2COL_D_KW];
     const int S = d[S2K_IM2COL_D_STRIDE], PT = d[S2K_IM2COL_D_PAD_T], PL = d[S2K_IM2COL_D_PAD_L], HO = d[S2K_IM2COL_D_HO], WO = d[S2K_IM2COL_D_WO];
@@ -1642,9 +1646,10 @@ __global__ void upsample_zero_kernel(const float* x, float* y, int H, int W, int
 }
 
 int launch_upsample_zero(const S2kOp& op, const Ctx& c) {
-    const float* x = ref_ptr<const float>(c, op.t[S2K_UPSAMPLE_ZERO_T_X]);
-    float* y = ref_ptr<float>(c, op.t[S2K_UPSAMPLE_ZERO_T_Y]);
-    CHECK_PTRS("upsample_zero", x, y);
+    Refs r(c);
+    const float* x = r.ptr<const float>(op.t[S2K_UPSAMPLE_ZERO_T_X]);
+    float* y = r.ptr<float>(op.t[S2K_UPSAMPLE_ZERO_T_Y]);
+    if (r.absent) return r.fault("upsample_zero");
     const int B = op.d[S2K_UPSAMPLE_ZERO_D_B], C = op.d[S2K_UPSAMPLE_ZERO_D_C], H = op.d[S2K_UPSAMPLE_ZERO_D_H], W = op.d[S2K_UPSAMPLE_ZERO_D_W];
     const int S = op.d[S2K_UPSAMPLE_ZERO_D_S], HO = op.d[S2K_UPSAMPLE_ZERO_D_HO], WO = op.d[S2K_UPSAMPLE_ZERO_D_WO];
     if (!x || !y || B <= 0 || C <= 0 || H <= 0 || W <= 0 || S <= 0 || HO <= 0 || WO <= 0) { set_error("upsample_zero: bad args"); return S2K_EINVAL; }
@@ -1689,9 +1694,13 @@ __global__ void adam_scalar_kernel(float* p, const float* g, float* m, float* v,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) adam_one(p[i], g[i], m[i], v[i], k);
 }
 
+int check_adam(float* p, const float* g, float* m, float* v, int64_t n, double, double, double, double, double, int step) {
+    if (!p || !g || !m || !v || n <= 0 || step <= 0) { set_error("adam: bad args"); return S2K_EINVAL; }
+    return S2K_OK;
+}
+
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double b1, double b2, double eps, double wd,
                 int step, hipStream_t st) {
-    if (!p || !g || !m || !v || n <= 0 || step <= 0) { set_error("adam: bad args"); return S2K_EINVAL; }
     const double c1 = 1.0 - pow(b1, (double)step), c2 = 1.0 - pow(b2, (double)step);
     AdamK k;
     k.lr_c1 = (float)(lr / c1);

@@ -16,15 +16,6 @@
 
 namespace s2k {
 
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-
 constexpr int SEG_CHUNK = 16384;        // floats per chunk (flat_stats.CHUNK): 256 threads x 16 quads
 constexpr int SEG_UNROLL = 4;           // 16-byte loads a thread keeps in flight
 
@@ -216,21 +207,15 @@ __global__ void __launch_bounds__(NTHREADS) grad_clip_kernel(float* X, const int
 }
 
 // ---- launchers: every check happens on the host before any HIP call ---------------------------------------------------------------
-static bool any_null_base(const void* const* ptrs, int n) {
-    for (int i = 0; i < n; ++i)
-        if (ptrs[i] == reinterpret_cast<const void*>(1)) return true;
-    return false;
-}
-
 int launch_seg_stats(const S2kOp& op, const Ctx& c) {
-    const float* X = ref_ptr<const float>(c, op.t[S2K_SEG_STATS_T_X]);
-    const int* segs = ref_ptr<const int>(c, op.t[S2K_SEG_STATS_T_SEGS]);
-    const int* chunks = ref_ptr<const int>(c, op.t[S2K_SEG_STATS_T_CHUNKS]);
-    double* part = ref_ptr<double>(c, op.t[S2K_SEG_STATS_T_PART]);
-    double* stats = ref_ptr<double>(c, op.t[S2K_SEG_STATS_T_STATS]);
-    long long* counts = ref_ptr<long long>(c, op.t[S2K_SEG_STATS_T_COUNTS]);
-    const void* ptrs[] = {X, segs, chunks, part, stats, counts};
-    if (any_null_base(ptrs, 6)) { set_error("seg_stats: tensor references a null base"); return S2K_EFAULT; }
+    Refs r(c);
+    const float* X = r.ptr<const float>(op.t[S2K_SEG_STATS_T_X]);
+    const int* segs = r.ptr<const int>(op.t[S2K_SEG_STATS_T_SEGS]);
+    const int* chunks = r.ptr<const int>(op.t[S2K_SEG_STATS_T_CHUNKS]);
+    double* part = r.ptr<double>(op.t[S2K_SEG_STATS_T_PART]);
+    double* stats = r.ptr<double>(op.t[S2K_SEG_STATS_T_STATS]);
+    long long* counts = r.ptr<long long>(op.t[S2K_SEG_STATS_T_COUNTS]);
+    if (r.absent) return r.fault("seg_stats");
     if (!X || !segs || !chunks || !part || !stats || !counts) { set_error("seg_stats: missing tensor"); return S2K_EINVAL; }
     const int P = op.d[S2K_SEG_STATS_D_P], NC = op.d[S2K_SEG_STATS_D_NC];
     if (P < 1 || NC < P) { set_error("seg_stats: bad dims (P >= 1 segments, NC >= P chunks)"); return S2K_EINVAL; }
@@ -248,13 +233,13 @@ static void launch_hist_r(unsigned grid, hipStream_t stream, const float* X, con
 }
 
 int launch_seg_hist(const S2kOp& op, const Ctx& c) {
-    const float* X = ref_ptr<const float>(c, op.t[S2K_SEG_HIST_T_X]);
-    const int* segs = ref_ptr<const int>(c, op.t[S2K_SEG_HIST_T_SEGS]);
-    const int* chunks = ref_ptr<const int>(c, op.t[S2K_SEG_HIST_T_CHUNKS]);
-    const double* stats = ref_ptr<const double>(c, op.t[S2K_SEG_HIST_T_STATS]);
-    unsigned long long* hist = ref_ptr<unsigned long long>(c, op.t[S2K_SEG_HIST_T_HIST]);
-    const void* ptrs[] = {X, segs, chunks, stats, hist};
-    if (any_null_base(ptrs, 5)) { set_error("seg_hist: tensor references a null base"); return S2K_EFAULT; }
+    Refs r(c);
+    const float* X = r.ptr<const float>(op.t[S2K_SEG_HIST_T_X]);
+    const int* segs = r.ptr<const int>(op.t[S2K_SEG_HIST_T_SEGS]);
+    const int* chunks = r.ptr<const int>(op.t[S2K_SEG_HIST_T_CHUNKS]);
+    const double* stats = r.ptr<const double>(op.t[S2K_SEG_HIST_T_STATS]);
+    unsigned long long* hist = r.ptr<unsigned long long>(op.t[S2K_SEG_HIST_T_HIST]);
+    if (r.absent) return r.fault("seg_hist");
     if (!X || !segs || !chunks || !stats || !hist) { set_error("seg_hist: missing tensor"); return S2K_EINVAL; }
     const int P = op.d[S2K_SEG_HIST_D_P], NC = op.d[S2K_SEG_HIST_D_NC], NB = op.d[S2K_SEG_HIST_D_NB];
     if (P < 1 || NC < P || NB < 1 || NB > 256) {
@@ -277,13 +262,13 @@ int launch_seg_hist(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_grad_clip(const S2kOp& op, const Ctx& c) {
-    float* X = ref_ptr<float>(c, op.t[S2K_GRAD_CLIP_T_X]);
-    const int* segs = ref_ptr<const int>(c, op.t[S2K_GRAD_CLIP_T_SEGS]);
-    const int* chunks = ref_ptr<const int>(c, op.t[S2K_GRAD_CLIP_T_CHUNKS]);
-    const double* stats = ref_ptr<const double>(c, op.t[S2K_GRAD_CLIP_T_STATS]);
-    float* norm = ref_ptr<float>(c, op.t[S2K_GRAD_CLIP_T_NORM]);
-    const void* ptrs[] = {X, segs, chunks, stats, norm};
-    if (any_null_base(ptrs, 5)) { set_error("grad_clip: tensor references a null base"); return S2K_EFAULT; }
+    Refs r(c);
+    float* X = r.ptr<float>(op.t[S2K_GRAD_CLIP_T_X]);
+    const int* segs = r.ptr<const int>(op.t[S2K_GRAD_CLIP_T_SEGS]);
+    const int* chunks = r.ptr<const int>(op.t[S2K_GRAD_CLIP_T_CHUNKS]);
+    const double* stats = r.ptr<const double>(op.t[S2K_GRAD_CLIP_T_STATS]);
+    float* norm = r.ptr<float>(op.t[S2K_GRAD_CLIP_T_NORM]);
+    if (r.absent) return r.fault("grad_clip");
     const int P = op.d[S2K_GRAD_CLIP_D_P], NC = op.d[S2K_GRAD_CLIP_D_NC], apply = op.d[S2K_GRAD_CLIP_D_APPLY];
     if (!stats || !norm || (apply && (!X || !segs || !chunks))) { set_error("grad_clip: missing tensor"); return S2K_EINVAL; }
     const float max_norm = op.f[S2K_GRAD_CLIP_F_MAX_NORM];

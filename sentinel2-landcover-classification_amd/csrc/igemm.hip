@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "plain.h"
 #include "igemm.h"
 
 namespace s2k {
@@ -589,15 +590,6 @@ __global__ void __launch_bounds__(NTHREADS, MINW) conv_igemm_kernel(const ConvP 
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);  // flagged by caller
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-
 static int pick_bm(int M) {
     // largest BM in {128, 64, 32} wasting <= 12 % of the rows, else the least wasteful
     const int cands[3] = {128, 64, 32};
@@ -726,32 +718,31 @@ static bool spatial_tiling(ConvP& p, int BN, int cap) {
 }
 
 int launch_conv(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     ConvP p{};
-    p.x1 = ref_ptr<const float>(c, op.t[S2K_CONV_T_X1]);
-    p.bnv1 = ref_ptr<const float>(c, op.t[S2K_CONV_T_BNV1]);
-    p.gate1 = ref_ptr<const float>(c, op.t[S2K_CONV_T_GATE1]);
-    p.x2 = ref_ptr<const float>(c, op.t[S2K_CONV_T_X2]);
-    p.bnv2 = ref_ptr<const float>(c, op.t[S2K_CONV_T_BNV2]);
-    p.wt = ref_ptr<const float>(c, op.t[S2K_CONV_T_WT]);
-    p.bias = ref_ptr<const float>(c, op.t[S2K_CONV_T_BIAS]);
-    p.y = ref_ptr<float>(c, op.t[S2K_CONV_T_Y]);
-    p.stats = ref_ptr<double>(c, op.t[S2K_CONV_T_STATS]);
-    p.res = ref_ptr<const float>(c, op.t[S2K_CONV_T_RES]);
-    p.scratch = ref_ptr<float>(c, op.t[S2K_CONV_T_SCRATCH]);
+    p.x1 = r.ptr<const float>(op.t[S2K_CONV_T_X1]);
+    p.bnv1 = r.ptr<const float>(op.t[S2K_CONV_T_BNV1]);
+    p.gate1 = r.ptr<const float>(op.t[S2K_CONV_T_GATE1]);
+    p.x2 = r.ptr<const float>(op.t[S2K_CONV_T_X2]);
+    p.bnv2 = r.ptr<const float>(op.t[S2K_CONV_T_BNV2]);
+    p.wt = r.ptr<const float>(op.t[S2K_CONV_T_WT]);
+    p.bias = r.ptr<const float>(op.t[S2K_CONV_T_BIAS]);
+    p.y = r.ptr<float>(op.t[S2K_CONV_T_Y]);
+    p.stats = r.ptr<double>(op.t[S2K_CONV_T_STATS]);
+    p.res = r.ptr<const float>(op.t[S2K_CONV_T_RES]);
+    p.scratch = r.ptr<float>(op.t[S2K_CONV_T_SCRATCH]);
     const bool split = (op.flags & S2K_FLAG_SPLIT) != 0;
     if (split && (op.flags & (S2K_FLAG_BF16 | S2K_FLAG_Q4 | S2K_FLAG_DMA | S2K_FLAG_RES_GELU_GRAD))) {
         set_error("conv: S2K_FLAG_SPLIT excludes S2K_FLAG_BF16 / Q4 / DMA / RES_GELU_GRAD"); return S2K_EINVAL;
     }
-    p.wtb = (op.flags & (S2K_FLAG_BF16 | S2K_FLAG_SPLIT)) ? ref_ptr<const void>(c, op.t[S2K_CONV_T_WTB]) : nullptr;
-    p.wtq = (!(op.flags & S2K_FLAG_BF16) && (op.flags & S2K_FLAG_Q4)) ? ref_ptr<const float>(c, op.t[S2K_CONV_T_WTB]) : nullptr;
+    p.wtb = (op.flags & (S2K_FLAG_BF16 | S2K_FLAG_SPLIT)) ? r.ptr<const void>(op.t[S2K_CONV_T_WTB]) : nullptr;
+    p.wtq = (!(op.flags & S2K_FLAG_BF16) && (op.flags & S2K_FLAG_Q4)) ? r.ptr<const float>(op.t[S2K_CONV_T_WTB]) : nullptr;
     p.force_dma = (op.flags & S2K_FLAG_DMA) ? 1 : 0;
     p.res_mul = (op.flags & S2K_FLAG_RES_GELU_GRAD) ? S2K_PRO_GELU : 0;
-    if (p.res_mul && (!p.res || (op.flags & S2K_FLAG_BF16))) { set_error("conv: S2K_FLAG_RES_GELU_GRAD needs RES and an f32 stage"); return S2K_EINVAL; }
+    if (p.res_mul && (op.t[S2K_CONV_T_RES] < 0 || (op.flags & S2K_FLAG_BF16))) { set_error("conv: S2K_FLAG_RES_GELU_GRAD needs RES and an f32 stage"); return S2K_EINVAL; }
     static const int cv_exp = tune_int("S2K_CV_EXP", 0);
     p.exp = cv_exp;
-    const void* ptrs[] = {p.x1, p.bnv1, p.gate1, p.x2, p.bnv2, p.wt, p.bias, p.y, p.stats, p.res, p.scratch, p.wtb, p.wtq};
-    for (const void* q : ptrs)
-        if (q == reinterpret_cast<const void*>(1)) { set_error("conv: tensor references a null base"); return S2K_EFAULT; }
+    if (r.absent) return r.fault("conv");
     const int32_t* d = op.d;
     p.B = d[S2K_CONV_D_B]; p.C1 = d[S2K_CONV_D_C1]; p.C2 = d[S2K_CONV_D_C2];
     p.H = d[S2K_CONV_D_H]; p.W = d[S2K_CONV_D_W]; p.M = d[S2K_CONV_D_M];
@@ -897,6 +888,11 @@ __global__ void mfma_selftest_kernel(const float* a, const float* b, float* d) {
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[l31 * 2 + lh], b[lh * 32 + l31], acc, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) d[((r & 3) + 8 * (r >> 2) + 4 * lh) * 32 + l31] = acc[r];
+}
+
+int check_mfma_selftest(const float* a, const float* b, float* d) {
+    if (!a || !b || !d) { set_error("selftest: null pointer"); return S2K_EINVAL; }
+    return S2K_OK;
 }
 
 int launch_mfma_selftest(const float* a, const float* b, float* d, hipStream_t st) {

@@ -10,15 +10,6 @@
 
 namespace s2k {
 
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-
 struct PrepP {
     const short* raw;
     const unsigned char* labels;
@@ -61,17 +52,16 @@ __global__ void __launch_bounds__(NTHREADS) tile_prep_kernel(const PrepP p) {
 // PARAMS are not range-checked on the device (that would cost a sync or a branch per element): the host mirror
 // (data/gpu_pipeline.py) draws / validates them before upload: 0 <= src < NSRC, 0 <= y0 <= H - S, 0 <= x0 <= W - S.
 int launch_tile_prep(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     PrepP p{};
-    p.raw = ref_ptr<const short>(c, op.t[S2K_TILE_PREP_T_RAW]);
-    p.labels = ref_ptr<const unsigned char>(c, op.t[S2K_TILE_PREP_T_LABELS]);
-    p.params = ref_ptr<const int>(c, op.t[S2K_TILE_PREP_T_PARAMS]);
-    p.norm = ref_ptr<const float>(c, op.t[S2K_TILE_PREP_T_NORM]);
-    p.lut = ref_ptr<const int>(c, op.t[S2K_TILE_PREP_T_LUT]);
-    p.x = ref_ptr<float>(c, op.t[S2K_TILE_PREP_T_X]);
-    p.y = ref_ptr<long long>(c, op.t[S2K_TILE_PREP_T_Y]);
-    const void* ptrs[] = {p.raw, p.labels, p.params, p.norm, p.lut, p.x, p.y};
-    for (const void* q : ptrs)
-        if (q == reinterpret_cast<const void*>(1)) { set_error("tile_prep: tensor references a null base"); return S2K_EFAULT; }
+    p.raw = r.ptr<const short>(op.t[S2K_TILE_PREP_T_RAW]);
+    p.labels = r.ptr<const unsigned char>(op.t[S2K_TILE_PREP_T_LABELS]);
+    p.params = r.ptr<const int>(op.t[S2K_TILE_PREP_T_PARAMS]);
+    p.norm = r.ptr<const float>(op.t[S2K_TILE_PREP_T_NORM]);
+    p.lut = r.ptr<const int>(op.t[S2K_TILE_PREP_T_LUT]);
+    p.x = r.ptr<float>(op.t[S2K_TILE_PREP_T_X]);
+    p.y = r.ptr<long long>(op.t[S2K_TILE_PREP_T_Y]);
+    if (r.absent) return r.fault("tile_prep");
     p.B = op.d[S2K_TILE_PREP_D_B]; p.C = op.d[S2K_TILE_PREP_D_C]; p.H = op.d[S2K_TILE_PREP_D_H]; p.W = op.d[S2K_TILE_PREP_D_W];
     p.S = op.d[S2K_TILE_PREP_D_S]; p.NSRC = op.d[S2K_TILE_PREP_D_NSRC];
     if (!p.raw || !p.params || !p.norm || !p.x || (p.y && (!p.labels || !p.lut))) { set_error("tile_prep: missing tensor"); return S2K_EINVAL; }
@@ -191,14 +181,13 @@ __global__ void __launch_bounds__(NTHREADS) tile_label_hist_kernel(const HistP p
 }
 
 int launch_tile_label_hist(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     HistP p{};
-    p.labels = ref_ptr<const unsigned char>(c, op.t[S2K_TILE_LABEL_HIST_T_LABELS]);
-    p.index = ref_ptr<const int>(c, op.t[S2K_TILE_LABEL_HIST_T_INDEX]);
-    p.lut = ref_ptr<const int>(c, op.t[S2K_TILE_LABEL_HIST_T_LUT]);
-    p.hist = ref_ptr<long long>(c, op.t[S2K_TILE_LABEL_HIST_T_HIST]);
-    const void* ptrs[] = {p.labels, p.index, p.lut, p.hist};
-    for (const void* q : ptrs)
-        if (q == reinterpret_cast<const void*>(1)) { set_error("tile_label_hist: tensor references a null base"); return S2K_EFAULT; }
+    p.labels = r.ptr<const unsigned char>(op.t[S2K_TILE_LABEL_HIST_T_LABELS]);
+    p.index = r.ptr<const int>(op.t[S2K_TILE_LABEL_HIST_T_INDEX]);
+    p.lut = r.ptr<const int>(op.t[S2K_TILE_LABEL_HIST_T_LUT]);
+    p.hist = r.ptr<long long>(op.t[S2K_TILE_LABEL_HIST_T_HIST]);
+    if (r.absent) return r.fault("tile_label_hist");
     if (!p.labels || !p.index || !p.lut || !p.hist) { set_error("tile_label_hist: missing tensor"); return S2K_EINVAL; }
     const int* d = op.d;
     p.M = d[S2K_TILE_LABEL_HIST_D_M]; p.H = d[S2K_TILE_LABEL_HIST_D_H]; p.W = d[S2K_TILE_LABEL_HIST_D_W]; p.K = d[S2K_TILE_LABEL_HIST_D_K];
@@ -292,14 +281,13 @@ __global__ void __launch_bounds__(NTHREADS) tile_moments_kernel(const MomP p) {
 }
 
 int launch_tile_moments(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     MomP p{};
-    p.raw = ref_ptr<const short>(c, op.t[S2K_TILE_MOMENTS_T_RAW]);
-    p.index = ref_ptr<const int>(c, op.t[S2K_TILE_MOMENTS_T_INDEX]);
-    p.sums = ref_ptr<unsigned long long>(c, op.t[S2K_TILE_MOMENTS_T_SUMS]);
-    p.sdpart = ref_ptr<double>(c, op.t[S2K_TILE_MOMENTS_T_SDPART]);
-    const void* ptrs[] = {p.raw, p.index, p.sums, p.sdpart};
-    for (const void* q : ptrs)
-        if (q == reinterpret_cast<const void*>(1)) { set_error("tile_moments: tensor references a null base"); return S2K_EFAULT; }
+    p.raw = r.ptr<const short>(op.t[S2K_TILE_MOMENTS_T_RAW]);
+    p.index = r.ptr<const int>(op.t[S2K_TILE_MOMENTS_T_INDEX]);
+    p.sums = r.ptr<unsigned long long>(op.t[S2K_TILE_MOMENTS_T_SUMS]);
+    p.sdpart = r.ptr<double>(op.t[S2K_TILE_MOMENTS_T_SDPART]);
+    if (r.absent) return r.fault("tile_moments");
     if (!p.raw || !p.index || !p.sums || !p.sdpart) { set_error("tile_moments: missing tensor"); return S2K_EINVAL; }
     p.M = op.d[S2K_TILE_MOMENTS_D_M]; p.C = op.d[S2K_TILE_MOMENTS_D_C]; p.NB = op.d[S2K_TILE_MOMENTS_D_NB];
     const int H = op.d[S2K_TILE_MOMENTS_D_H], W = op.d[S2K_TILE_MOMENTS_D_W], nsrc = op.d[S2K_TILE_MOMENTS_D_NSRC];

@@ -26,15 +26,6 @@ struct LossP {
     float gamma, smooth;
 };
 
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-static bool bad(const void* q) { return q == reinterpret_cast<const void*>(1); }
 
 // pow(om, g) for the exponents the configs use (gamma = 2 in the benchmark recipe) without the general powf
 __device__ __forceinline__ float pow_gamma(float om, float g) {
@@ -244,14 +235,15 @@ static int fill(LossP& p, const S2kOp& op, const Ctx& c, bool bwd) {
 }
 
 int launch_loss_fwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     LossP p{};
     if (int e = fill(p, op, c, false)) return e;
-    p.logits = ref_ptr<const float>(c, op.t[S2K_LOSS_FWD_T_LOGITS]);
-    p.labels = ref_ptr<const int64_t>(c, op.t[S2K_LOSS_FWD_T_LABELS]);
-    p.alpha = ref_ptr<const float>(c, op.t[S2K_LOSS_FWD_T_ALPHA]);
-    p.loss = ref_ptr<float>(c, op.t[S2K_LOSS_FWD_T_LOSS]);
-    p.acc = ref_ptr<double>(c, op.t[S2K_LOSS_FWD_T_ACC]);
-    if (bad(p.logits) || bad(p.labels) || bad(p.alpha) || bad(p.loss) || bad(p.acc)) { set_error("loss_fwd: null base"); return S2K_EFAULT; }
+    p.logits = r.ptr<const float>(op.t[S2K_LOSS_FWD_T_LOGITS]);
+    p.labels = r.ptr<const int64_t>(op.t[S2K_LOSS_FWD_T_LABELS]);
+    p.alpha = r.ptr<const float>(op.t[S2K_LOSS_FWD_T_ALPHA]);
+    p.loss = r.ptr<float>(op.t[S2K_LOSS_FWD_T_LOSS]);
+    p.acc = r.ptr<double>(op.t[S2K_LOSS_FWD_T_ACC]);
+    if (r.absent) { set_error("loss_fwd: null base"); return S2K_EFAULT; }
     if (!p.logits || !p.labels || !p.loss || !p.acc) { set_error("loss_fwd: missing tensor"); return S2K_EINVAL; }
     if (hipMemsetAsync(p.acc, 0, 2 * sizeof(double), c.stream) != hipSuccess) { set_error("loss_fwd: memset failed"); return S2K_EHIP; }
     if (p.B > 65535) { set_error("loss: batch beyond the launch grid"); return S2K_EINVAL; }
@@ -267,15 +259,16 @@ int launch_loss_fwd(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_loss_bwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     LossP p{};
     if (int e = fill(p, op, c, true)) return e;
-    p.logits = ref_ptr<const float>(c, op.t[S2K_LOSS_BWD_T_LOGITS]);
-    p.labels = ref_ptr<const int64_t>(c, op.t[S2K_LOSS_BWD_T_LABELS]);
-    p.alpha = ref_ptr<const float>(c, op.t[S2K_LOSS_BWD_T_ALPHA]);
-    p.acc = ref_ptr<double>(c, op.t[S2K_LOSS_BWD_T_ACC]);
-    p.gout = ref_ptr<const float>(c, op.t[S2K_LOSS_BWD_T_GOUT]);
-    p.dlogits = ref_ptr<float>(c, op.t[S2K_LOSS_BWD_T_DLOGITS]);
-    if (bad(p.logits) || bad(p.labels) || bad(p.alpha) || bad(p.acc) || bad(p.gout) || bad(p.dlogits)) { set_error("loss_bwd: null base"); return S2K_EFAULT; }
+    p.logits = r.ptr<const float>(op.t[S2K_LOSS_BWD_T_LOGITS]);
+    p.labels = r.ptr<const int64_t>(op.t[S2K_LOSS_BWD_T_LABELS]);
+    p.alpha = r.ptr<const float>(op.t[S2K_LOSS_BWD_T_ALPHA]);
+    p.acc = r.ptr<double>(op.t[S2K_LOSS_BWD_T_ACC]);
+    p.gout = r.ptr<const float>(op.t[S2K_LOSS_BWD_T_GOUT]);
+    p.dlogits = r.ptr<float>(op.t[S2K_LOSS_BWD_T_DLOGITS]);
+    if (r.absent) { set_error("loss_bwd: null base"); return S2K_EFAULT; }
     if (!p.logits || !p.labels || !p.acc || !p.dlogits) { set_error("loss_bwd: missing tensor"); return S2K_EINVAL; }
     if (p.B > 65535) { set_error("loss: batch beyond the launch grid"); return S2K_EINVAL; }
     const dim3 grid(pixel_blocks(p.B, p.HW), (unsigned)p.B);
@@ -289,9 +282,10 @@ int launch_loss_bwd(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_argmax(const S2kOp& op, const Ctx& c) {
-    const float* logits = ref_ptr<const float>(c, op.t[S2K_ARGMAX_T_LOGITS]);
-    int64_t* mask = ref_ptr<int64_t>(c, op.t[S2K_ARGMAX_T_MASK]);
-    if (bad(logits) || bad(mask)) { set_error("argmax: null base"); return S2K_EFAULT; }
+    Refs r(c);
+    const float* logits = r.ptr<const float>(op.t[S2K_ARGMAX_T_LOGITS]);
+    int64_t* mask = r.ptr<int64_t>(op.t[S2K_ARGMAX_T_MASK]);
+    if (r.absent) { set_error("argmax: null base"); return S2K_EFAULT; }
     const int B = op.d[S2K_ARGMAX_D_B], C = op.d[S2K_ARGMAX_D_C], HW = op.d[S2K_ARGMAX_D_HW];
     if (!logits || !mask || B <= 0 || C <= 0 || HW <= 0) { set_error("argmax: bad args"); return S2K_EINVAL; }
     if (B > 65535) { set_error("argmax: batch beyond the launch grid"); return S2K_EINVAL; }
@@ -317,10 +311,11 @@ __global__ void __launch_bounds__(NTHREADS) confusion_kernel(const int64_t* pred
 }
 
 int launch_confusion(const S2kOp& op, const Ctx& c) {
-    const int64_t* pred = ref_ptr<const int64_t>(c, op.t[S2K_CONFUSION_T_PRED]);
-    const int64_t* labels = ref_ptr<const int64_t>(c, op.t[S2K_CONFUSION_T_LABELS]);
-    unsigned long long* hist = ref_ptr<unsigned long long>(c, op.t[S2K_CONFUSION_T_HIST]);
-    if (bad(pred) || bad(labels) || bad(hist)) { set_error("confusion: null base"); return S2K_EFAULT; }
+    Refs r(c);
+    const int64_t* pred = r.ptr<const int64_t>(op.t[S2K_CONFUSION_T_PRED]);
+    const int64_t* labels = r.ptr<const int64_t>(op.t[S2K_CONFUSION_T_LABELS]);
+    unsigned long long* hist = r.ptr<unsigned long long>(op.t[S2K_CONFUSION_T_HIST]);
+    if (r.absent) { set_error("confusion: null base"); return S2K_EFAULT; }
     const int64_t n = op.n[S2K_CONFUSION_N_COUNT];
     const int C = op.d[S2K_CONFUSION_D_C];
     if (!pred || !labels || !hist || n <= 0 || C <= 0 || C > MAXC) { set_error("confusion: bad args (C <= %d)", MAXC); return S2K_EINVAL; }

@@ -15,7 +15,7 @@
 // floats, IMGS gives P contiguous floats per (channel, row), and OUT only 3*P contiguous bytes per patch row - the four waves together
 // write 12*P.  The per-patch sums are wave reductions in f64 in a fixed lane order (no atomics): results repeat from run to run.
 // All indexing derives from the dimensions the launcher validated; there are no index tables on the device.
-#include "common.h"
+#include "plain.h"
 
 namespace s2k {
 

@@ -14,15 +14,6 @@
 
 namespace s2k {
 
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-
 constexpr int BLEND_MAXK = 32;
 
 struct BlendP {
@@ -192,21 +183,20 @@ static void launch_k(const BlendP& p, int mode, unsigned grid, hipStream_t strea
 // YS / XS / FLIPS / INDEX are not range-checked against the tile on the device beyond what keeps every access inside its tensor (a
 // window position is always formed from a local coordinate inside [0, S)); the host (predict.py) builds and validates them.
 int launch_window_blend(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     BlendP p{};
-    p.logits = ref_ptr<const float>(c, op.t[S2K_WINDOW_BLEND_T_LOGITS]);
-    p.ys = ref_ptr<const int>(c, op.t[S2K_WINDOW_BLEND_T_YS]);
-    p.xs = ref_ptr<const int>(c, op.t[S2K_WINDOW_BLEND_T_XS]);
-    p.flips = ref_ptr<const int>(c, op.t[S2K_WINDOW_BLEND_T_FLIPS]);
-    p.w1 = ref_ptr<const float>(c, op.t[S2K_WINDOW_BLEND_T_W1]);
-    p.blend = ref_ptr<float>(c, op.t[S2K_WINDOW_BLEND_T_BLEND]);
-    p.mask = ref_ptr<long long>(c, op.t[S2K_WINDOW_BLEND_T_MASK]);
-    p.labels = ref_ptr<const unsigned char>(c, op.t[S2K_WINDOW_BLEND_T_LABELS]);
-    p.index = ref_ptr<const int>(c, op.t[S2K_WINDOW_BLEND_T_INDEX]);
-    p.lut = ref_ptr<const int>(c, op.t[S2K_WINDOW_BLEND_T_LUT]);
-    p.hist = ref_ptr<unsigned long long>(c, op.t[S2K_WINDOW_BLEND_T_HIST]);
-    const void* ptrs[] = {p.logits, p.ys, p.xs, p.flips, p.w1, p.blend, p.mask, p.labels, p.index, p.lut, p.hist};
-    for (const void* q : ptrs)
-        if (q == reinterpret_cast<const void*>(1)) { set_error("window_blend: tensor references a null base"); return S2K_EFAULT; }
+    p.logits = r.ptr<const float>(op.t[S2K_WINDOW_BLEND_T_LOGITS]);
+    p.ys = r.ptr<const int>(op.t[S2K_WINDOW_BLEND_T_YS]);
+    p.xs = r.ptr<const int>(op.t[S2K_WINDOW_BLEND_T_XS]);
+    p.flips = r.ptr<const int>(op.t[S2K_WINDOW_BLEND_T_FLIPS]);
+    p.w1 = r.ptr<const float>(op.t[S2K_WINDOW_BLEND_T_W1]);
+    p.blend = r.ptr<float>(op.t[S2K_WINDOW_BLEND_T_BLEND]);
+    p.mask = r.ptr<long long>(op.t[S2K_WINDOW_BLEND_T_MASK]);
+    p.labels = r.ptr<const unsigned char>(op.t[S2K_WINDOW_BLEND_T_LABELS]);
+    p.index = r.ptr<const int>(op.t[S2K_WINDOW_BLEND_T_INDEX]);
+    p.lut = r.ptr<const int>(op.t[S2K_WINDOW_BLEND_T_LUT]);
+    p.hist = r.ptr<unsigned long long>(op.t[S2K_WINDOW_BLEND_T_HIST]);
+    if (r.absent) return r.fault("window_blend");
     if (!p.logits || !p.ys || !p.xs || !p.flips || !p.w1) { set_error("window_blend: missing tensor"); return S2K_EINVAL; }
     const int* d = op.d;
     p.M = d[S2K_WINDOW_BLEND_D_M]; p.F = d[S2K_WINDOW_BLEND_D_F]; p.NY = d[S2K_WINDOW_BLEND_D_NY]; p.NX = d[S2K_WINDOW_BLEND_D_NX];

@@ -12,21 +12,6 @@
 
 namespace s2k {
 
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-
-static bool any_null_base(const void* const* ptrs, int n) {
-    for (int i = 0; i < n; ++i)
-        if (ptrs[i] == reinterpret_cast<const void*>(1)) return true;
-    return false;
-}
-
 // ---- TILE_RADIX_HIST ------------------------------------------------------------------------------------------------------------
 constexpr int RSEL_CHUNK = 16384;       // values per work item: 256 threads x 8 vectors of 8 int16
 constexpr int RSEL_UNROLL = 4;          // 16-byte loads a thread keeps in flight
@@ -168,14 +153,14 @@ __global__ void __launch_bounds__(NTHREADS) tile_radix_hist_kernel(const RadixP 
 }
 
 int launch_tile_radix_hist(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     RadixP p{};
-    p.raw = ref_ptr<const short>(c, op.t[S2K_TILE_RADIX_HIST_T_RAW]);
-    p.index = ref_ptr<const int>(c, op.t[S2K_TILE_RADIX_HIST_T_INDEX]);
-    p.bands = ref_ptr<const int>(c, op.t[S2K_TILE_RADIX_HIST_T_BANDS]);
-    p.bucket = ref_ptr<const int>(c, op.t[S2K_TILE_RADIX_HIST_T_BUCKET]);
-    p.hist = ref_ptr<unsigned long long>(c, op.t[S2K_TILE_RADIX_HIST_T_HIST]);
-    const void* ptrs[] = {p.raw, p.index, p.bands, p.bucket, p.hist};
-    if (any_null_base(ptrs, 5)) { set_error("tile_radix_hist: tensor references a null base"); return S2K_EFAULT; }
+    p.raw = r.ptr<const short>(op.t[S2K_TILE_RADIX_HIST_T_RAW]);
+    p.index = r.ptr<const int>(op.t[S2K_TILE_RADIX_HIST_T_INDEX]);
+    p.bands = r.ptr<const int>(op.t[S2K_TILE_RADIX_HIST_T_BANDS]);
+    p.bucket = r.ptr<const int>(op.t[S2K_TILE_RADIX_HIST_T_BUCKET]);
+    p.hist = r.ptr<unsigned long long>(op.t[S2K_TILE_RADIX_HIST_T_HIST]);
+    if (r.absent) return r.fault("tile_radix_hist");
     const int* d = op.d;
     const int pass = d[S2K_TILE_RADIX_HIST_D_PASS];
     if (!p.raw || !p.index || !p.bands || !p.hist || (pass == 1 && !p.bucket)) { set_error("tile_radix_hist: missing tensor"); return S2K_EINVAL; }
@@ -276,16 +261,16 @@ __global__ void __launch_bounds__(NTHREADS) tile_rank_pick_kernel(const PickP p)
 }
 
 int launch_tile_rank_pick(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     PickP p{};
-    p.hist = ref_ptr<const long long>(c, op.t[S2K_TILE_RANK_PICK_T_HIST]);
-    p.ranks = ref_ptr<const long long>(c, op.t[S2K_TILE_RANK_PICK_T_RANKS]);
-    p.bucket = ref_ptr<int>(c, op.t[S2K_TILE_RANK_PICK_T_BUCKET]);
-    p.rest = ref_ptr<long long>(c, op.t[S2K_TILE_RANK_PICK_T_REST]);
-    p.values = ref_ptr<int>(c, op.t[S2K_TILE_RANK_PICK_T_VALUES]);
-    p.frac = ref_ptr<const double>(c, op.t[S2K_TILE_RANK_PICK_T_FRAC]);
-    p.pct = ref_ptr<double>(c, op.t[S2K_TILE_RANK_PICK_T_PCT]);
-    const void* ptrs[] = {p.hist, p.ranks, p.bucket, p.rest, p.values, p.frac, p.pct};
-    if (any_null_base(ptrs, 7)) { set_error("tile_rank_pick: tensor references a null base"); return S2K_EFAULT; }
+    p.hist = r.ptr<const long long>(op.t[S2K_TILE_RANK_PICK_T_HIST]);
+    p.ranks = r.ptr<const long long>(op.t[S2K_TILE_RANK_PICK_T_RANKS]);
+    p.bucket = r.ptr<int>(op.t[S2K_TILE_RANK_PICK_T_BUCKET]);
+    p.rest = r.ptr<long long>(op.t[S2K_TILE_RANK_PICK_T_REST]);
+    p.values = r.ptr<int>(op.t[S2K_TILE_RANK_PICK_T_VALUES]);
+    p.frac = r.ptr<const double>(op.t[S2K_TILE_RANK_PICK_T_FRAC]);
+    p.pct = r.ptr<double>(op.t[S2K_TILE_RANK_PICK_T_PCT]);
+    if (r.absent) return r.fault("tile_rank_pick");
     const int step = op.d[S2K_TILE_RANK_PICK_D_STEP];
     p.G = op.d[S2K_TILE_RANK_PICK_D_G]; p.R = op.d[S2K_TILE_RANK_PICK_D_R];
     const int64_t N = op.n[S2K_TILE_RANK_PICK_N_N];
@@ -367,15 +352,15 @@ __global__ void __launch_bounds__(NTHREADS) tile_quicklook_kernel(const LookP p)
 
 // PARAMS, SLOT and BANDS are not range-checked on the device: the host (data/quicklook.py) validates them before upload.
 int launch_tile_quicklook(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     LookP p{};
-    p.raw = ref_ptr<const short>(c, op.t[S2K_TILE_QUICKLOOK_T_RAW]);
-    p.params = ref_ptr<const int>(c, op.t[S2K_TILE_QUICKLOOK_T_PARAMS]);
-    p.slot = ref_ptr<const int>(c, op.t[S2K_TILE_QUICKLOOK_T_SLOT]);
-    p.bands = ref_ptr<const int>(c, op.t[S2K_TILE_QUICKLOOK_T_BANDS]);
-    p.pct = ref_ptr<const double>(c, op.t[S2K_TILE_QUICKLOOK_T_PCT]);
-    p.out = ref_ptr<unsigned char>(c, op.t[S2K_TILE_QUICKLOOK_T_OUT]);
-    const void* ptrs[] = {p.raw, p.params, p.slot, p.bands, p.pct, p.out};
-    if (any_null_base(ptrs, 6)) { set_error("tile_quicklook: tensor references a null base"); return S2K_EFAULT; }
+    p.raw = r.ptr<const short>(op.t[S2K_TILE_QUICKLOOK_T_RAW]);
+    p.params = r.ptr<const int>(op.t[S2K_TILE_QUICKLOOK_T_PARAMS]);
+    p.slot = r.ptr<const int>(op.t[S2K_TILE_QUICKLOOK_T_SLOT]);
+    p.bands = r.ptr<const int>(op.t[S2K_TILE_QUICKLOOK_T_BANDS]);
+    p.pct = r.ptr<const double>(op.t[S2K_TILE_QUICKLOOK_T_PCT]);
+    p.out = r.ptr<unsigned char>(op.t[S2K_TILE_QUICKLOOK_T_OUT]);
+    if (r.absent) return r.fault("tile_quicklook");
     if (!p.raw || !p.params || !p.slot || !p.bands || !p.pct || !p.out) { set_error("tile_quicklook: missing tensor"); return S2K_EINVAL; }
     const int* d = op.d;
     p.B = d[S2K_TILE_QUICKLOOK_D_B]; p.C = d[S2K_TILE_QUICKLOOK_D_C]; p.H = d[S2K_TILE_QUICKLOOK_D_H]; p.W = d[S2K_TILE_QUICKLOOK_D_W];
@@ -457,13 +442,13 @@ __global__ void __launch_bounds__(NTHREADS) class_overlay_kernel(const OverP p) 
 }
 
 int launch_class_overlay(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     OverP p{};
-    p.cls = ref_ptr<const long long>(c, op.t[S2K_CLASS_OVERLAY_T_CLS]);
-    p.palette = ref_ptr<const unsigned char>(c, op.t[S2K_CLASS_OVERLAY_T_PALETTE]);
-    p.base = ref_ptr<const unsigned char>(c, op.t[S2K_CLASS_OVERLAY_T_BASE]);
-    p.out = ref_ptr<unsigned char>(c, op.t[S2K_CLASS_OVERLAY_T_OUT]);
-    const void* ptrs[] = {p.cls, p.palette, p.base, p.out};
-    if (any_null_base(ptrs, 4)) { set_error("class_overlay: tensor references a null base"); return S2K_EFAULT; }
+    p.cls = r.ptr<const long long>(op.t[S2K_CLASS_OVERLAY_T_CLS]);
+    p.palette = r.ptr<const unsigned char>(op.t[S2K_CLASS_OVERLAY_T_PALETTE]);
+    p.base = r.ptr<const unsigned char>(op.t[S2K_CLASS_OVERLAY_T_BASE]);
+    p.out = r.ptr<unsigned char>(op.t[S2K_CLASS_OVERLAY_T_OUT]);
+    if (r.absent) return r.fault("class_overlay");
     if (!p.cls || !p.palette || !p.out) { set_error("class_overlay: missing tensor"); return S2K_EINVAL; }
     const int* d = op.d;
     const int B = d[S2K_CLASS_OVERLAY_D_B], SH = d[S2K_CLASS_OVERLAY_D_SH], SW = d[S2K_CLASS_OVERLAY_D_SW];

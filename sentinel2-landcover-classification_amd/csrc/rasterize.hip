@@ -28,7 +28,7 @@
 // RAST_BLOCK_H, a list by S, a vertex range by V - whatever the tables hold.  Every index read from a table is clamped before it is
 // used, every coordinate to +-RAST_MAX_COORD, every origin to +-RAST_MAX_ORIGIN, so that tables the host could not see do no harm: they
 // set a bit in `status` and the output is then not to be used.  Tile offsets are 64-bit, offsets inside a tile 32-bit.
-#include "common.h"
+#include "plain.h"
 
 #include <climits>
 

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "plain.h"
 
 namespace s2k {
 
@@ -82,47 +83,14 @@ int launch_tile_rank_pick(const S2kOp&, const Ctx&);
 int launch_tile_quicklook(const S2kOp&, const Ctx&);
 int launch_class_overlay(const S2kOp&, const Ctx&);
 int launch_dw_bwd_chain(const S2kOp*, const Ctx&);
-int launch_adam(float*, const float*, float*, float*, int64_t, double, double, double, double, double, int, hipStream_t);
-int launch_mfma_selftest(const float*, const float*, float*, hipStream_t);
-int check_mae_panels(const float*, const float*, const float*, const float*, const double*, unsigned char*, float*, int, int, int, int,
-                     int, int, int, const int*, int, const int*, int, int, int);
-int launch_mae_panels(const float*, const float*, const float*, const float*, const double*, unsigned char*, float*, int, int, int, int,
-                      int, int, int, const int*, int, const int*, int, int, int, hipStream_t);
-int check_classmap_filter(const void*, int, const int*, void*, int, int, int, int, int, int, int, unsigned, unsigned, int, const unsigned char*,
-                          const int*, const int*, int, unsigned long long*, unsigned long long*);
-int launch_classmap_filter(const void*, int, const int*, void*, int, int, int, int, int, int, int, unsigned, unsigned, int, const unsigned char*,
-                           const int*, const int*, int, unsigned long long*, unsigned long long*, hipStream_t);
-int check_classmap_components(const void*, int, const int*, int, int, int, int, int, unsigned, int*, int*, unsigned long long*, unsigned*);
-int launch_classmap_components(const void*, int, const int*, int, int, int, int, int, unsigned, int*, int*, unsigned long long*, unsigned*,
-                               hipStream_t);
-int check_classmap_sieve(const void*, int, const int*, void*, int, int, int, int, int, int, unsigned, int, const int*, const int*,
-                         unsigned long long*, const unsigned char*, const int*, const int*, int, unsigned long long*, unsigned long long*,
-                         unsigned*);
-int launch_classmap_sieve(const void*, int, const int*, void*, int, int, int, int, int, int, unsigned, int, const int*, const int*,
-                          unsigned long long*, const unsigned char*, const int*, const int*, int, unsigned long long*, unsigned long long*,
-                          unsigned*, hipStream_t);
-int check_classmap_distance(const void*, int, const int*, int, int, int, int, int, unsigned, int, unsigned, void*, int*, int*, const void*, int,
-                            const int*, int, unsigned long long*);
-int launch_classmap_distance(const void*, int, const int*, int, int, int, int, int, unsigned, int, unsigned, void*, int*, int*, const void*, int,
-                             const int*, int, unsigned long long*, hipStream_t);
-size_t classmap_distance_workspace(int, int, int);
-int check_calibration(const float*, int, const void*, int, const int*, int, int, int, unsigned, const float*, int, int, int, float, int, float*,
-                      void*, int, unsigned long long*, unsigned long long*, unsigned long long*);
-int launch_calibration(const float*, int, const void*, int, const int*, int, int, int, unsigned, const float*, int, int, int, float, int, float*,
-                       void*, int, unsigned long long*, unsigned long long*, unsigned long long*, hipStream_t);
-int check_rasterize(const int*, int, const int*, const int*, int, const int*, int, const int*, int, int, int, void*, int, int, int, int, void*,
-                    long long*, int*);
-int launch_rasterize(const int*, int, const int*, const int*, int, const int*, int, const int*, int, int, int, void*, int, int, int, int, void*,
-                     long long*, int*, hipStream_t);
-size_t rasterize_workspace(int, int);
 
 static int launch_memset(const S2kOp& op, const Ctx& c) {
     const int64_t ref = op.t[S2K_MEMSET_T_DST];
     const int64_t bytes = op.n[S2K_MEMSET_N_BYTES];
     if (ref < 0 || bytes <= 0) { set_error("memset: bad args"); return S2K_EINVAL; }
-    const int base = (int)(ref >> 56);
-    if (base >= c.n_bases || !c.bases[base]) { set_error("memset: null base %d", base); return S2K_EFAULT; }
-    char* dst = static_cast<char*>(c.bases[base]) + (ref & ((1ll << 56) - 1));
+    Refs r(c);
+    char* dst = r.ptr<char>(ref);
+    if (r.absent) { set_error("memset: null base %d", Refs::base_of(ref)); return S2K_EFAULT; }
     if (hipMemsetAsync(dst, 0, (size_t)bytes, c.stream) != hipSuccess) { set_error("memset: hipMemsetAsync failed"); return S2K_EHIP; }
     return S2K_OK;
 }
@@ -335,9 +303,18 @@ static int try_dw_chain(const S2kOp* ops, int i, int end, const Ctx& c, int* rc)
     const int HW = H * W;
     if (a1.d[S2K_BN_BWD_APPLY_D_B] != B || a1.d[S2K_BN_BWD_APPLY_D_C] != C || a1.d[S2K_BN_BWD_APPLY_D_HW] != HW ||
         a2.d[S2K_BN_BWD_APPLY_D_B] != B || a2.d[S2K_BN_BWD_APPLY_D_C] != C || a2.d[S2K_BN_BWD_APPLY_D_HW] != HW) return 0;
-    g_s2k_variant = 0;
     *rc = check_launch(launch_dw_bwd_chain(&ops[i], c), ops[i], i);
     return 4;
+}
+
+// Issues ops[i] on c.stream: the depthwise backward chain that starts there as one launch, else the record's own stage.  *rc is the
+// status; returns the number of records consumed (4 or 1).  g_s2k_variant then names the kernel family the launcher picked.
+static int issue_step(const S2kOp* ops, int i, int end, const Ctx& c, int* rc) {
+    g_s2k_variant = 0;
+    const int used = try_dw_chain(ops, i, end, c, rc);
+    if (used) return used;
+    *rc = check_launch(dispatch(ops[i], c), ops[i], i);
+    return 1;
 }
 
 int s2k_program_run(const S2kOp* ops, int begin, int end, void* const* bases, int n_bases, void* stream) {
@@ -359,30 +336,21 @@ int s2k_program_run(const S2kOp* ops, int begin, int end, void* const* bases, in
     int rc = S2K_OK;
     for (int i = begin; i < end; ++i) {
         const S2kOp& op = ops[i];
-        if ((op.flags & S2K_FLAG_CHAIN) && i + 3 < end) {
-            // a join asked for by any record of the chain is honoured in front of it (merely early if the chain is then declined); the
-            // consumed DWCONV_WGRAD is not issued to the side stream
-            if ((op.flags | ops[i + 1].flags | ops[i + 2].flags | ops[i + 3].flags) & S2K_FLAG_JOIN) join();
-            const int used = try_dw_chain(ops, i, end, c, &rc);
-            if (used) {
-                main_dirty = true;
-                if (rc != S2K_OK) break;
-                i += used - 1;
-                continue;
-            }
-        }
-        if ((op.flags & S2K_FLAG_SIDE) && sq) {
+        // a join asked for by any record of a chain is honoured in front of it (merely early if the chain is then declined)
+        const bool chain = (op.flags & S2K_FLAG_CHAIN) && i + 3 < end;
+        if (chain && ((op.flags | ops[i + 1].flags | ops[i + 2].flags | ops[i + 3].flags) & S2K_FLAG_JOIN)) join();
+        if ((op.flags & S2K_FLAG_SIDE) && sq && !chain) {     // (a chain runs on the caller's stream)
             if (main_dirty) {
                 (void)hipEventRecord(sq->fork, main_st);
                 (void)hipStreamWaitEvent(sq->stream, sq->fork, 0);
                 main_dirty = false;
             }
             Ctx cs{bases, n_bases, sq->stream};
-            rc = check_launch(dispatch(op, cs), op, i);
+            i += issue_step(ops, i, end, cs, &rc) - 1;
             side_busy = true;
         } else {
             if (op.flags & S2K_FLAG_JOIN) join();
-            rc = check_launch(dispatch(op, c), op, i);
+            i += issue_step(ops, i, end, c, &rc) - 1;    // a chain consumes its DWCONV_WGRAD: that record is not issued to the side stream
             main_dirty = true;
         }
         if (rc != S2K_OK) break;
@@ -439,16 +407,14 @@ static int profile_impl(const S2kOp* ops, int begin, int end, void* const* bases
     int done = 0;
     std::vector<char> fused(n, 0);      // records consumed by the launch of an earlier one: 0 ms, no launch of their own
     for (int i = 0; i < n; ++i) {
-        g_s2k_variant = 0;
-        const int used = try_dw_chain(ops, begin + i, end, c, &rc);
-        if (!used) rc = check_launch(dispatch(ops[begin + i], c), ops[begin + i], begin + i);
+        const int used = issue_step(ops, begin + i, end, c, &rc);
         if (rc != S2K_OK) break;
-        for (int k = 0; k < (used ? used : 1); ++k) {
+        for (int k = 0; k < used; ++k) {
             if (variant_per_op) variant_per_op[i + k] = g_s2k_variant;
             hipEventRecord(ev[i + k + 1], st);
             if (k) fused[i + k] = 1;
         }
-        if (used) i += used - 1;
+        i += used - 1;
         done = i + 1;
     }
     hipStreamSynchronize(st);
@@ -467,93 +433,70 @@ static int profile_impl(const S2kOp* ops, int begin, int end, void* const* bases
     return rc;
 }
 
-int s2k_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
-                  double weight_decay, int step, void* stream) {
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    const int rc = launch_adam(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, static_cast<hipStream_t>(stream));
+}  // extern "C"
+
+namespace {
+
+template <typename T>
+struct as_given { using type = T; };
+
+// Every plain C-ABI function (csrc/plain.h) is this sequence: validate all arguments with no HIP call before it, make the device that
+// owns the stream current, launch, report a launch error as "<name>: <hip error>".  A... is deduced from check's signature alone.
+template <typename... A>
+int guarded_call(const char* name, void* stream, int (*check)(A...), int (*launch)(A..., hipStream_t), typename as_given<A>::type... args) {
+    const int bad = check(args...);
+    if (bad != S2K_OK) return bad;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DeviceGuard guard(st);
+    const int rc = launch(args..., st);
     if (rc != S2K_OK) return rc;
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("adam: %s", hipGetErrorString(e)); return S2K_EHIP; }
+    if (e != hipSuccess) { set_error("%s: %s", name, hipGetErrorString(e)); return S2K_EHIP; }
     return S2K_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int s2k_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int step, void* stream) {
+    return guarded_call("adam", stream, check_adam, launch_adam, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step);
 }
 
 int s2k_mae_panels(const float* imgs, const float* pred, const float* mask, const float* norm, const double* bounds, unsigned char* out,
                    float* patch_mse, int B, int C, int T, int H, int W, int P, int TUB, const int* bands, int frame, const int* panels,
                    int n_panels, int fill, int norm_pix, void* stream) {
-    // every argument is validated before the first HIP call (the device guard's included)
-    const int bad = check_mae_panels(imgs, pred, mask, norm, bounds, out, patch_mse, B, C, T, H, W, P, TUB, bands, frame, panels, n_panels,
-                                     fill, norm_pix);
-    if (bad != S2K_OK) return bad;
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    const int rc = launch_mae_panels(imgs, pred, mask, norm, bounds, out, patch_mse, B, C, T, H, W, P, TUB, bands, frame, panels, n_panels,
-                                     fill, norm_pix, static_cast<hipStream_t>(stream));
-    if (rc != S2K_OK) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("mae_panels: %s", hipGetErrorString(e)); return S2K_EHIP; }
-    return S2K_OK;
+    return guarded_call("mae_panels", stream, check_mae_panels, launch_mae_panels, imgs, pred, mask, norm, bounds, out, patch_mse, B, C, T, H, W,
+                        P, TUB, bands, frame, panels, n_panels, fill, norm_pix);
 }
 
 int s2k_classmap_filter(const void* src, int src_bytes, const int* src_lut, void* dst, int dst_bytes, int M, int H, int W, int K, int size,
                         int mode, unsigned votes, unsigned fixed, int ignore, const unsigned char* labels, const int* index, const int* lut,
                         int nsrc, unsigned long long* hist, unsigned long long* changed, void* stream) {
-    // every argument is validated before the first HIP call (the device guard's included)
-    const int bad = check_classmap_filter(src, src_bytes, src_lut, dst, dst_bytes, M, H, W, K, size, mode, votes, fixed, ignore, labels, index,
-                                          lut, nsrc, hist, changed);
-    if (bad != S2K_OK) return bad;
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    const int rc = launch_classmap_filter(src, src_bytes, src_lut, dst, dst_bytes, M, H, W, K, size, mode, votes, fixed, ignore, labels, index,
-                                          lut, nsrc, hist, changed, static_cast<hipStream_t>(stream));
-    if (rc != S2K_OK) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("classmap_filter: %s", hipGetErrorString(e)); return S2K_EHIP; }
-    return S2K_OK;
+    return guarded_call("classmap_filter", stream, check_classmap_filter, launch_classmap_filter, src, src_bytes, src_lut, dst, dst_bytes, M, H,
+                        W, K, size, mode, votes, fixed, ignore, labels, index, lut, nsrc, hist, changed);
 }
 
 int s2k_classmap_components(const void* src, int src_bytes, const int* src_lut, int M, int H, int W, int K, int connectivity,
                             unsigned exclude, int* labels, int* areas, unsigned long long* counts, unsigned* status, void* stream) {
-    // every argument is validated before the first HIP call (the device guard's included)
-    const int bad = check_classmap_components(src, src_bytes, src_lut, M, H, W, K, connectivity, exclude, labels, areas, counts, status);
-    if (bad != S2K_OK) return bad;
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    const int rc = launch_classmap_components(src, src_bytes, src_lut, M, H, W, K, connectivity, exclude, labels, areas, counts, status,
-                                              static_cast<hipStream_t>(stream));
-    if (rc != S2K_OK) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("classmap_components: %s", hipGetErrorString(e)); return S2K_EHIP; }
-    return S2K_OK;
+    return guarded_call("classmap_components", stream, check_classmap_components, launch_classmap_components, src, src_bytes, src_lut, M, H, W,
+                        K, connectivity, exclude, labels, areas, counts, status);
 }
 
 int s2k_classmap_sieve(const void* src, int src_bytes, const int* src_lut, void* dst, int dst_bytes, int M, int H, int W, int K,
                        int min_area, unsigned fixed, int to, const int* labels, const int* areas, unsigned long long* best,
                        const unsigned char* hist_labels, const int* index, const int* lut, int nsrc, unsigned long long* hist,
                        unsigned long long* changed, unsigned* status, void* stream) {
-    // every argument is validated before the first HIP call (the device guard's included)
-    const int bad = check_classmap_sieve(src, src_bytes, src_lut, dst, dst_bytes, M, H, W, K, min_area, fixed, to, labels, areas, best,
-                                         hist_labels, index, lut, nsrc, hist, changed, status);
-    if (bad != S2K_OK) return bad;
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    const int rc = launch_classmap_sieve(src, src_bytes, src_lut, dst, dst_bytes, M, H, W, K, min_area, fixed, to, labels, areas, best,
-                                         hist_labels, index, lut, nsrc, hist, changed, status, static_cast<hipStream_t>(stream));
-    if (rc != S2K_OK) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("classmap_sieve: %s", hipGetErrorString(e)); return S2K_EHIP; }
-    return S2K_OK;
+    return guarded_call("classmap_sieve", stream, check_classmap_sieve, launch_classmap_sieve, src, src_bytes, src_lut, dst, dst_bytes, M, H, W,
+                        K, min_area, fixed, to, labels, areas, best, hist_labels, index, lut, nsrc, hist, changed, status);
 }
 
 int s2k_classmap_distance(const void* src, int src_bytes, const int* src_lut, int M, int H, int W, int K, int mode, unsigned sites,
                           int connectivity, unsigned exclude, void* work, int* dist2, int* nearest, const void* other, int other_bytes,
                           const int* edges, int n_edges, unsigned long long* hist, void* stream) {
-    // every argument is validated before the first HIP call (the device guard's included)
-    const int bad = check_classmap_distance(src, src_bytes, src_lut, M, H, W, K, mode, sites, connectivity, exclude, work, dist2, nearest, other,
-                                            other_bytes, edges, n_edges, hist);
-    if (bad != S2K_OK) return bad;
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    const int rc = launch_classmap_distance(src, src_bytes, src_lut, M, H, W, K, mode, sites, connectivity, exclude, work, dist2, nearest, other,
-                                            other_bytes, edges, n_edges, hist, static_cast<hipStream_t>(stream));
-    if (rc != S2K_OK) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("classmap_distance: %s", hipGetErrorString(e)); return S2K_EHIP; }
-    return S2K_OK;
+    return guarded_call("classmap_distance", stream, check_classmap_distance, launch_classmap_distance, src, src_bytes, src_lut, M, H, W, K,
+                        mode, sites, connectivity, exclude, work, dist2, nearest, other, other_bytes, edges, n_edges, hist);
 }
 
 size_t s2k_classmap_distance_workspace(int M, int H, int W) { return classmap_distance_workspace(M, H, W); }
@@ -562,44 +505,21 @@ int s2k_calibration(const float* scores, int mode, const void* labels, int label
                     unsigned exclude, const float* temps, int n_temps, int bins, int measure, float reject_below, int reject_to, float* conf,
                     void* pred, int pred_bytes, unsigned long long* hist, unsigned long long* totals, unsigned long long* skipped,
                     void* stream) {
-    // every argument is validated before the first HIP call (the device guard's included)
-    const int bad = check_calibration(scores, mode, labels, label_bytes, label_lut, N, K, P, exclude, temps, n_temps, bins, measure, reject_below,
-                                      reject_to, conf, pred, pred_bytes, hist, totals, skipped);
-    if (bad != S2K_OK) return bad;
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    const int rc = launch_calibration(scores, mode, labels, label_bytes, label_lut, N, K, P, exclude, temps, n_temps, bins, measure, reject_below,
-                                      reject_to, conf, pred, pred_bytes, hist, totals, skipped, static_cast<hipStream_t>(stream));
-    if (rc != S2K_OK) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("calibration: %s", hipGetErrorString(e)); return S2K_EHIP; }
-    return S2K_OK;
+    return guarded_call("calibration", stream, check_calibration, launch_calibration, scores, mode, labels, label_bytes, label_lut, N, K, P,
+                        exclude, temps, n_temps, bins, measure, reject_below, reject_to, conf, pred, pred_bytes, hist, totals, skipped);
 }
 
 int s2k_rasterize(const int* verts, int V, const int* ring_start, const int* ring_shape, int R, const int* values, int S, const int* origins,
                   int M, int H, int W, void* dst, int dst_bytes, int mode, int burn, int fill, void* work, long long* unfilled, int* status,
                   void* stream) {
-    // every argument is validated before the first HIP call (the device guard's included)
-    const int bad = check_rasterize(verts, V, ring_start, ring_shape, R, values, S, origins, M, H, W, dst, dst_bytes, mode, burn, fill, work,
-                                    unfilled, status);
-    if (bad != S2K_OK) return bad;
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    const int rc = launch_rasterize(verts, V, ring_start, ring_shape, R, values, S, origins, M, H, W, dst, dst_bytes, mode, burn, fill, work,
-                                    unfilled, status, static_cast<hipStream_t>(stream));
-    if (rc != S2K_OK) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("rasterize: %s", hipGetErrorString(e)); return S2K_EHIP; }
-    return S2K_OK;
+    return guarded_call("rasterize", stream, check_rasterize, launch_rasterize, verts, V, ring_start, ring_shape, R, values, S, origins, M, H, W,
+                        dst, dst_bytes, mode, burn, fill, work, unfilled, status);
 }
 
 size_t s2k_rasterize_workspace(int M, int S) { return rasterize_workspace(M, S); }
 
 int s2k_selftest_mfma(const float* a, const float* b, float* d, void* stream) {
-    if (!a || !b || !d) { set_error("selftest: null pointer"); return S2K_EINVAL; }
-    DeviceGuard guard(static_cast<hipStream_t>(stream));
-    launch_mfma_selftest(a, b, d, static_cast<hipStream_t>(stream));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("selftest: %s", hipGetErrorString(e)); return S2K_EHIP; }
-    return S2K_OK;
+    return guarded_call("selftest", stream, check_mfma_selftest, launch_mfma_selftest, a, b, d);
 }
 
 }  // extern "C"

@@ -10,22 +10,6 @@
 
 namespace s2k {
 
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-static bool bad(const void* q) { return q == reinterpret_cast<const void*>(1); }
-#define CHECK_PTRS(name, ...)                                                                         \
-    do {                                                                                              \
-        const void* _ps[] = {__VA_ARGS__};                                                            \
-        for (const void* _q : _ps)                                                                    \
-            if (bad(_q)) { set_error(name ": tensor references a null base"); return S2K_EFAULT; }    \
-    } while (0)
-
 // ---------------- channel LayerNorm ---------------------------------------------------------------------
 // One workgroup = 64 consecutive positions (lanes) of one sample x all C channels; the four waves split the
 // channels, combine their per-position sums through LDS, then each normalises its own channels.
@@ -250,13 +234,14 @@ __global__ void __launch_bounds__(64 * LN_NW) chan_ln_fwd_kernel(const LnP p) {
 }
 
 int launch_chan_ln_fwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     LnP p{};
-    p.x = ref_ptr<const float>(c, op.t[S2K_CHAN_LN_FWD_T_X]);
-    p.gamma = ref_ptr<const float>(c, op.t[S2K_CHAN_LN_FWD_T_GAMMA]);
-    p.beta = ref_ptr<const float>(c, op.t[S2K_CHAN_LN_FWD_T_BETA]);
-    p.y = ref_ptr<float>(c, op.t[S2K_CHAN_LN_FWD_T_Y]);
-    p.mr = ref_ptr<float>(c, op.t[S2K_CHAN_LN_FWD_T_MR]);
-    CHECK_PTRS("chan_ln_fwd", p.x, p.gamma, p.beta, p.y, p.mr);
+    p.x = r.ptr<const float>(op.t[S2K_CHAN_LN_FWD_T_X]);
+    p.gamma = r.ptr<const float>(op.t[S2K_CHAN_LN_FWD_T_GAMMA]);
+    p.beta = r.ptr<const float>(op.t[S2K_CHAN_LN_FWD_T_BETA]);
+    p.y = r.ptr<float>(op.t[S2K_CHAN_LN_FWD_T_Y]);
+    p.mr = r.ptr<float>(op.t[S2K_CHAN_LN_FWD_T_MR]);
+    if (r.absent) return r.fault("chan_ln_fwd");
     p.B = op.d[S2K_CHAN_LN_FWD_D_B]; p.C = op.d[S2K_CHAN_LN_FWD_D_C]; p.HW = op.d[S2K_CHAN_LN_FWD_D_HW];
     p.eps = op.f[S2K_CHAN_LN_FWD_F_EPS];
     if (!p.x || !p.gamma || !p.beta || !p.y || !p.mr || p.B <= 0 || p.C <= 0 || p.HW <= 0) { set_error("chan_ln_fwd: bad args"); return S2K_EINVAL; }
@@ -378,17 +363,18 @@ __global__ void __launch_bounds__(64 * LN_NW) chan_ln_bwd_kernel(const LnP p) {
 }
 
 int launch_chan_ln_bwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     LnP p{};
-    p.dy = ref_ptr<const float>(c, op.t[S2K_CHAN_LN_BWD_T_DY]);
-    p.x = ref_ptr<const float>(c, op.t[S2K_CHAN_LN_BWD_T_X]);
-    p.mr_in = ref_ptr<const float>(c, op.t[S2K_CHAN_LN_BWD_T_MR]);
-    p.gamma = ref_ptr<const float>(c, op.t[S2K_CHAN_LN_BWD_T_GAMMA]);
-    p.dx = ref_ptr<float>(c, op.t[S2K_CHAN_LN_BWD_T_DX]);
-    p.dgamma = ref_ptr<float>(c, op.t[S2K_CHAN_LN_BWD_T_DGAMMA]);
-    p.dbeta = ref_ptr<float>(c, op.t[S2K_CHAN_LN_BWD_T_DBETA]);
-    p.dxin = ref_ptr<const float>(c, op.t[S2K_CHAN_LN_BWD_T_DXIN]);
-    p.dsum = ref_ptr<float>(c, op.t[S2K_CHAN_LN_BWD_T_DSUM]);
-    CHECK_PTRS("chan_ln_bwd", p.dy, p.x, p.mr_in, p.gamma, p.dx, p.dgamma, p.dbeta, p.dxin, p.dsum);
+    p.dy = r.ptr<const float>(op.t[S2K_CHAN_LN_BWD_T_DY]);
+    p.x = r.ptr<const float>(op.t[S2K_CHAN_LN_BWD_T_X]);
+    p.mr_in = r.ptr<const float>(op.t[S2K_CHAN_LN_BWD_T_MR]);
+    p.gamma = r.ptr<const float>(op.t[S2K_CHAN_LN_BWD_T_GAMMA]);
+    p.dx = r.ptr<float>(op.t[S2K_CHAN_LN_BWD_T_DX]);
+    p.dgamma = r.ptr<float>(op.t[S2K_CHAN_LN_BWD_T_DGAMMA]);
+    p.dbeta = r.ptr<float>(op.t[S2K_CHAN_LN_BWD_T_DBETA]);
+    p.dxin = r.ptr<const float>(op.t[S2K_CHAN_LN_BWD_T_DXIN]);
+    p.dsum = r.ptr<float>(op.t[S2K_CHAN_LN_BWD_T_DSUM]);
+    if (r.absent) return r.fault("chan_ln_bwd");
     p.B = op.d[S2K_CHAN_LN_BWD_D_B]; p.C = op.d[S2K_CHAN_LN_BWD_D_C]; p.HW = op.d[S2K_CHAN_LN_BWD_D_HW];
     p.accum = op.d[S2K_CHAN_LN_BWD_D_ACCUM];
     if (!p.dy || !p.x || !p.mr_in || !p.gamma || !p.dx || p.B <= 0 || p.C <= 0 || p.HW <= 0 || (!p.dgamma != !p.dbeta)) {
@@ -409,9 +395,10 @@ __global__ void act_bwd_kernel(float* g, const float* x, int64_t n, int act) {
 }
 
 int launch_act_bwd(const S2kOp& op, const Ctx& c) {
-    float* g = ref_ptr<float>(c, op.t[S2K_ACT_BWD_T_G]);
-    const float* x = ref_ptr<const float>(c, op.t[S2K_ACT_BWD_T_X]);
-    CHECK_PTRS("act_bwd", g, x);
+    Refs r(c);
+    float* g = r.ptr<float>(op.t[S2K_ACT_BWD_T_G]);
+    const float* x = r.ptr<const float>(op.t[S2K_ACT_BWD_T_X]);
+    if (r.absent) return r.fault("act_bwd");
     const int64_t n = op.n[S2K_ACT_BWD_N_COUNT];
     const int act = op.d[S2K_ACT_BWD_D_ACT];
     if (!g || !x || n <= 0 || (act != S2K_PRO_GELU && act != S2K_PRO_SILU && act != S2K_PRO_RELU && act != 5)) { set_error("act_bwd: bad args"); return S2K_EINVAL; }
@@ -454,11 +441,12 @@ __global__ void __launch_bounds__(256) act_gate_planes_kernel(const float* x, fl
 }
 
 int launch_act_fwd(const S2kOp& op, const Ctx& c) {
-    const float* x = ref_ptr<const float>(c, op.t[S2K_ACT_FWD_T_X]);
-    float* y = ref_ptr<float>(c, op.t[S2K_ACT_FWD_T_Y]);
-    const float* bnv = ref_ptr<const float>(c, op.t[S2K_ACT_FWD_T_BNV]);
-    const float* gate = ref_ptr<const float>(c, op.t[S2K_ACT_FWD_T_GATE]);
-    CHECK_PTRS("act_fwd", x, y, bnv, gate);
+    Refs r(c);
+    const float* x = r.ptr<const float>(op.t[S2K_ACT_FWD_T_X]);
+    float* y = r.ptr<float>(op.t[S2K_ACT_FWD_T_Y]);
+    const float* bnv = r.ptr<const float>(op.t[S2K_ACT_FWD_T_BNV]);
+    const float* gate = r.ptr<const float>(op.t[S2K_ACT_FWD_T_GATE]);
+    if (r.absent) return r.fault("act_fwd");
     if (gate) {
         const int64_t n = op.n[S2K_ACT_FWD_N_COUNT];
         const int C = op.d[S2K_ACT_FWD_D_C], HW = op.d[S2K_ACT_FWD_D_HW];
@@ -487,9 +475,10 @@ __global__ void drop_gate_kernel(const float* u, float* gate, int64_t n, float p
 }
 
 int launch_drop_gate(const S2kOp& op, const Ctx& c) {
-    const float* u = ref_ptr<const float>(c, op.t[S2K_DROP_GATE_T_U]);
-    float* gate = ref_ptr<float>(c, op.t[S2K_DROP_GATE_T_GATE]);
-    CHECK_PTRS("drop_gate", u, gate);
+    Refs r(c);
+    const float* u = r.ptr<const float>(op.t[S2K_DROP_GATE_T_U]);
+    float* gate = r.ptr<float>(op.t[S2K_DROP_GATE_T_GATE]);
+    if (r.absent) return r.fault("drop_gate");
     const int64_t n = op.n[S2K_DROP_GATE_N_COUNT];
     const float prob = op.f[S2K_DROP_GATE_F_P];
     if (!u || !gate || n <= 0 || !(prob >= 0.0f && prob < 1.0f)) { set_error("drop_gate: bad args"); return S2K_EINVAL; }
@@ -524,12 +513,13 @@ __global__ void __launch_bounds__(NTHREADS) mae_mask_index_kernel(const float* n
 }
 
 int launch_mae_mask_index(const S2kOp& op, const Ctx& c) {
-    const float* noise = ref_ptr<const float>(c, op.t[S2K_MAE_MASK_INDEX_T_NOISE]);
-    int64_t* ids = ref_ptr<int64_t>(c, op.t[S2K_MAE_MASK_INDEX_T_IDS_RESTORE]);
-    float* mask = ref_ptr<float>(c, op.t[S2K_MAE_MASK_INDEX_T_MASK]);
-    int* enc = ref_ptr<int>(c, op.t[S2K_MAE_MASK_INDEX_T_ENC_IDX]);
-    int* dec = ref_ptr<int>(c, op.t[S2K_MAE_MASK_INDEX_T_DEC_IDX]);
-    CHECK_PTRS("mae_mask_index", noise, ids, mask, enc, dec);
+    Refs r(c);
+    const float* noise = r.ptr<const float>(op.t[S2K_MAE_MASK_INDEX_T_NOISE]);
+    int64_t* ids = r.ptr<int64_t>(op.t[S2K_MAE_MASK_INDEX_T_IDS_RESTORE]);
+    float* mask = r.ptr<float>(op.t[S2K_MAE_MASK_INDEX_T_MASK]);
+    int* enc = r.ptr<int>(op.t[S2K_MAE_MASK_INDEX_T_ENC_IDX]);
+    int* dec = r.ptr<int>(op.t[S2K_MAE_MASK_INDEX_T_DEC_IDX]);
+    if (r.absent) return r.fault("mae_mask_index");
     const int B = op.d[S2K_MAE_MASK_INDEX_D_B], L = op.d[S2K_MAE_MASK_INDEX_D_L], keep = op.d[S2K_MAE_MASK_INDEX_D_KEEP];
     if (!noise || !ids || !mask || !enc || !dec || B <= 0 || L <= 0 || keep < 0 || keep > L || L > 12288) { set_error("mae_mask_index: bad args"); return S2K_EINVAL; }
     hipLaunchKernelGGL(mae_mask_index_kernel, dim3(B), dim3(NTHREADS), (size_t)L * sizeof(float), c.stream, noise, ids, mask, enc, dec, L, keep);
@@ -563,13 +553,14 @@ __global__ void token_gather_kernel(const TokP p) {
 }
 
 int launch_token_gather(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     TokP p{};
-    p.in = ref_ptr<const float>(c, op.t[S2K_TOKEN_GATHER_T_IN]);
-    p.idx = ref_ptr<const int>(c, op.t[S2K_TOKEN_GATHER_T_IDX]);
-    p.fill = ref_ptr<const float>(c, op.t[S2K_TOKEN_GATHER_T_FILL]);
-    p.pos = ref_ptr<const float>(c, op.t[S2K_TOKEN_GATHER_T_POS]);
-    p.out = ref_ptr<float>(c, op.t[S2K_TOKEN_GATHER_T_OUT]);
-    CHECK_PTRS("token_gather", p.in, p.idx, p.fill, p.pos, p.out);
+    p.in = r.ptr<const float>(op.t[S2K_TOKEN_GATHER_T_IN]);
+    p.idx = r.ptr<const int>(op.t[S2K_TOKEN_GATHER_T_IDX]);
+    p.fill = r.ptr<const float>(op.t[S2K_TOKEN_GATHER_T_FILL]);
+    p.pos = r.ptr<const float>(op.t[S2K_TOKEN_GATHER_T_POS]);
+    p.out = r.ptr<float>(op.t[S2K_TOKEN_GATHER_T_OUT]);
+    if (r.absent) return r.fault("token_gather");
     p.B = op.d[S2K_TOKEN_GATHER_D_B]; p.C = op.d[S2K_TOKEN_GATHER_D_C]; p.Lin = op.d[S2K_TOKEN_GATHER_D_LIN];
     p.Lout = op.d[S2K_TOKEN_GATHER_D_LOUT]; p.pos_by_src = op.d[S2K_TOKEN_GATHER_D_POS_BY_SRC]; p.pos_off = op.d[S2K_TOKEN_GATHER_D_POS_OFF];
     p.LinS = op.d[S2K_TOKEN_GATHER_D_LIN_S] > 0 ? op.d[S2K_TOKEN_GATHER_D_LIN_S] : p.Lin;
@@ -615,12 +606,13 @@ __global__ void __launch_bounds__(NTHREADS) token_scatter_kernel(const TokP p) {
 }
 
 int launch_token_scatter(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     TokP p{};
-    p.dout = ref_ptr<const float>(c, op.t[S2K_TOKEN_SCATTER_T_DOUT]);
-    p.idx = ref_ptr<const int>(c, op.t[S2K_TOKEN_SCATTER_T_IDX]);
-    p.din = ref_ptr<float>(c, op.t[S2K_TOKEN_SCATTER_T_DIN]);
-    p.dfill = ref_ptr<float>(c, op.t[S2K_TOKEN_SCATTER_T_DFILL]);
-    CHECK_PTRS("token_scatter", p.dout, p.idx, p.din, p.dfill);
+    p.dout = r.ptr<const float>(op.t[S2K_TOKEN_SCATTER_T_DOUT]);
+    p.idx = r.ptr<const int>(op.t[S2K_TOKEN_SCATTER_T_IDX]);
+    p.din = r.ptr<float>(op.t[S2K_TOKEN_SCATTER_T_DIN]);
+    p.dfill = r.ptr<float>(op.t[S2K_TOKEN_SCATTER_T_DFILL]);
+    if (r.absent) return r.fault("token_scatter");
     p.B = op.d[S2K_TOKEN_SCATTER_D_B]; p.C = op.d[S2K_TOKEN_SCATTER_D_C]; p.Lin = op.d[S2K_TOKEN_SCATTER_D_LIN]; p.Lout = op.d[S2K_TOKEN_SCATTER_D_LOUT];
     p.LinS = op.d[S2K_TOKEN_SCATTER_D_LIN_S] > 0 ? op.d[S2K_TOKEN_SCATTER_D_LIN_S] : p.Lin;
     p.LoutS = op.d[S2K_TOKEN_SCATTER_D_LOUT_S] > 0 ? op.d[S2K_TOKEN_SCATTER_D_LOUT_S] : p.Lout;
@@ -715,12 +707,13 @@ __global__ void __launch_bounds__(NTHREADS) patch_norm_target_grad_kernel(const 
 }
 
 int launch_patchify(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     PatchP p{};
     if (int e = fill_patch(p, op.d)) return e;
-    p.x = ref_ptr<const float>(c, op.t[S2K_PATCHIFY_T_X]);
-    p.out = ref_ptr<float>(c, op.t[S2K_PATCHIFY_T_OUT]);
-    const float* imgs = ref_ptr<const float>(c, op.t[S2K_PATCHIFY_T_IMGS]);
-    CHECK_PTRS("patchify", p.x, p.out, imgs);
+    p.x = r.ptr<const float>(op.t[S2K_PATCHIFY_T_X]);
+    p.out = r.ptr<float>(op.t[S2K_PATCHIFY_T_OUT]);
+    const float* imgs = r.ptr<const float>(op.t[S2K_PATCHIFY_T_IMGS]);
+    if (r.absent) return r.fault("patchify");
     if (!p.x || !p.out) { set_error("patchify: missing tensor"); return S2K_EINVAL; }
     const int inverse = op.d[S2K_PATCHIFY_D_INVERSE], order = op.d[S2K_PATCHIFY_D_ORDER], l_off = op.d[S2K_PATCHIFY_D_L_OFF];
     const int ls = op.d[S2K_PATCHIFY_D_LS] > 0 ? op.d[S2K_PATCHIFY_D_LS] : p.L;
@@ -878,14 +871,15 @@ static int mae_loss_common(PatchP& p, const S2kOp& op) {
 }
 
 int launch_mae_loss_fwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     PatchP p{};
     if (int e = mae_loss_common(p, op)) return e;
-    p.pred = ref_ptr<const float>(c, op.t[S2K_MAE_LOSS_FWD_T_PRED]);
-    p.x = ref_ptr<const float>(c, op.t[S2K_MAE_LOSS_FWD_T_IMGS]);
-    p.mask = ref_ptr<const float>(c, op.t[S2K_MAE_LOSS_FWD_T_MASK]);
-    p.loss = ref_ptr<float>(c, op.t[S2K_MAE_LOSS_FWD_T_LOSS]);
-    p.acc = ref_ptr<double>(c, op.t[S2K_MAE_LOSS_FWD_T_ACC]);
-    CHECK_PTRS("mae_loss_fwd", p.pred, p.x, p.mask, p.loss, p.acc);
+    p.pred = r.ptr<const float>(op.t[S2K_MAE_LOSS_FWD_T_PRED]);
+    p.x = r.ptr<const float>(op.t[S2K_MAE_LOSS_FWD_T_IMGS]);
+    p.mask = r.ptr<const float>(op.t[S2K_MAE_LOSS_FWD_T_MASK]);
+    p.loss = r.ptr<float>(op.t[S2K_MAE_LOSS_FWD_T_LOSS]);
+    p.acc = r.ptr<double>(op.t[S2K_MAE_LOSS_FWD_T_ACC]);
+    if (r.absent) return r.fault("mae_loss_fwd");
     if (!p.pred || !p.x || !p.mask || !p.loss || !p.acc) { set_error("mae_loss_fwd: missing tensor"); return S2K_EINVAL; }
     (void)hipMemsetAsync(p.acc, 0, 2 * sizeof(double), c.stream);
     const dim3 grid((unsigned)cdiv(p.LP, 256), (unsigned)(p.TUB * p.P), (unsigned)p.B);
@@ -896,15 +890,16 @@ int launch_mae_loss_fwd(const S2kOp& op, const Ctx& c) {
 }
 
 int launch_mae_loss_bwd(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     PatchP p{};
     if (int e = mae_loss_common(p, op)) return e;
-    p.pred = ref_ptr<const float>(c, op.t[S2K_MAE_LOSS_BWD_T_PRED]);
-    p.x = ref_ptr<const float>(c, op.t[S2K_MAE_LOSS_BWD_T_IMGS]);
-    p.mask = ref_ptr<const float>(c, op.t[S2K_MAE_LOSS_BWD_T_MASK]);
-    p.acc = ref_ptr<double>(c, op.t[S2K_MAE_LOSS_BWD_T_ACC]);
-    p.gout = ref_ptr<const float>(c, op.t[S2K_MAE_LOSS_BWD_T_GOUT]);
-    p.dpred = ref_ptr<float>(c, op.t[S2K_MAE_LOSS_BWD_T_DPRED]);
-    CHECK_PTRS("mae_loss_bwd", p.pred, p.x, p.mask, p.acc, p.gout, p.dpred);
+    p.pred = r.ptr<const float>(op.t[S2K_MAE_LOSS_BWD_T_PRED]);
+    p.x = r.ptr<const float>(op.t[S2K_MAE_LOSS_BWD_T_IMGS]);
+    p.mask = r.ptr<const float>(op.t[S2K_MAE_LOSS_BWD_T_MASK]);
+    p.acc = r.ptr<double>(op.t[S2K_MAE_LOSS_BWD_T_ACC]);
+    p.gout = r.ptr<const float>(op.t[S2K_MAE_LOSS_BWD_T_GOUT]);
+    p.dpred = r.ptr<float>(op.t[S2K_MAE_LOSS_BWD_T_DPRED]);
+    if (r.absent) return r.fault("mae_loss_bwd");
     if (!p.pred || !p.x || !p.mask || !p.acc || !p.dpred) { set_error("mae_loss_bwd: missing tensor"); return S2K_EINVAL; }
     const dim3 grid((unsigned)cdiv(p.LP, 256), (unsigned)(p.TUB * p.P), (unsigned)p.B);
     if (mae_vec(p)) hipLaunchKernelGGL((mae_loss_rows_kernel<true, true>), grid, dim3(256), 0, c.stream, p);
@@ -931,9 +926,10 @@ __global__ void __launch_bounds__(NTHREADS) transpose_cl_kernel(const float* x, 
 }
 
 int launch_transpose_cl(const S2kOp& op, const Ctx& c) {
-    const float* x = ref_ptr<const float>(c, op.t[S2K_TRANSPOSE_CL_T_X]);
-    float* y = ref_ptr<float>(c, op.t[S2K_TRANSPOSE_CL_T_Y]);
-    CHECK_PTRS("transpose_cl", x, y);
+    Refs r(c);
+    const float* x = r.ptr<const float>(op.t[S2K_TRANSPOSE_CL_T_X]);
+    float* y = r.ptr<float>(op.t[S2K_TRANSPOSE_CL_T_Y]);
+    if (r.absent) return r.fault("transpose_cl");
     const int B = op.d[S2K_TRANSPOSE_CL_D_B], C = op.d[S2K_TRANSPOSE_CL_D_C], L = op.d[S2K_TRANSPOSE_CL_D_L];
     const int l_off = op.d[S2K_TRANSPOSE_CL_D_L_OFF], Lout = op.d[S2K_TRANSPOSE_CL_D_LOUT];
     int ys = op.d[S2K_TRANSPOSE_CL_D_YS], y_off = op.d[S2K_TRANSPOSE_CL_D_Y_OFF];
@@ -960,9 +956,10 @@ __global__ void ids_to_dec_idx_kernel(const int64_t* ids, int* dec, int B, int L
 }
 
 int launch_ids_to_dec_idx(const S2kOp& op, const Ctx& c) {
-    const int64_t* ids = ref_ptr<const int64_t>(c, op.t[S2K_IDS_TO_DEC_IDX_T_IDS]);
-    int* dec = ref_ptr<int>(c, op.t[S2K_IDS_TO_DEC_IDX_T_DEC_IDX]);
-    CHECK_PTRS("ids_to_dec_idx", ids, dec);
+    Refs r(c);
+    const int64_t* ids = r.ptr<const int64_t>(op.t[S2K_IDS_TO_DEC_IDX_T_IDS]);
+    int* dec = r.ptr<int>(op.t[S2K_IDS_TO_DEC_IDX_T_DEC_IDX]);
+    if (r.absent) return r.fault("ids_to_dec_idx");
     const int B = op.d[S2K_IDS_TO_DEC_IDX_D_B], L = op.d[S2K_IDS_TO_DEC_IDX_D_L], keep = op.d[S2K_IDS_TO_DEC_IDX_D_KEEP];
     if (!ids || !dec || B <= 0 || L <= 0 || keep < 0) { set_error("ids_to_dec_idx: bad args"); return S2K_EINVAL; }
     const int64_t n = (int64_t)B * (1 + L);

@@ -362,15 +362,6 @@ __global__ void __launch_bounds__(NTHREADS) wgrad_kernel(const WgradP p) {
 }
 
 // -------------------------------------------------------------------------------------------------
-template <typename T>
-static T* ref_ptr(const Ctx& c, int64_t ref) {
-    if (ref < 0) return nullptr;
-    const int base = (int)(ref >> 56);
-    const int64_t off = ref & ((1ll << 56) - 1);
-    if (base >= c.n_bases || c.bases[base] == nullptr) return reinterpret_cast<T*>(1);
-    return reinterpret_cast<T*>(static_cast<char*>(c.bases[base]) + off);
-}
-
 template <int MODE, int T, int WM, int WN, int WVM, int WVN, int WVK, int NPJ, int EPT, int PROP, int PROQ, int WSC = 0>
 static int launch_wg2(WgradP& p, hipStream_t st) {
     constexpr int BM = WM * WVM * 32, BC = WN * WVN * 32;
@@ -449,17 +440,16 @@ static int launch_wg(WgradP& p, hipStream_t st) {
 }
 
 int launch_wgrad(const S2kOp& op, const Ctx& c) {
+    Refs r(c);
     WgradP p{};
-    p.p = ref_ptr<const float>(c, op.t[S2K_WGRAD_T_P]);
-    p.bnvp = ref_ptr<const float>(c, op.t[S2K_WGRAD_T_BNVP]);
-    p.gatep = ref_ptr<const float>(c, op.t[S2K_WGRAD_T_GATEP]);
-    p.q = ref_ptr<const float>(c, op.t[S2K_WGRAD_T_Q]);
-    p.bnvq = ref_ptr<const float>(c, op.t[S2K_WGRAD_T_BNVQ]);
-    p.gateq = ref_ptr<const float>(c, op.t[S2K_WGRAD_T_GATEQ]);
-    p.wgs = ref_ptr<float>(c, op.t[S2K_WGRAD_T_WGS]);
-    const void* ptrs[] = {p.p, p.bnvp, p.gatep, p.q, p.bnvq, p.gateq, p.wgs};
-    for (const void* q : ptrs)
-        if (q == reinterpret_cast<const void*>(1)) { set_error("wgrad: tensor references a null base"); return S2K_EFAULT; }
+    p.p = r.ptr<const float>(op.t[S2K_WGRAD_T_P]);
+    p.bnvp = r.ptr<const float>(op.t[S2K_WGRAD_T_BNVP]);
+    p.gatep = r.ptr<const float>(op.t[S2K_WGRAD_T_GATEP]);
+    p.q = r.ptr<const float>(op.t[S2K_WGRAD_T_Q]);
+    p.bnvq = r.ptr<const float>(op.t[S2K_WGRAD_T_BNVQ]);
+    p.gateq = r.ptr<const float>(op.t[S2K_WGRAD_T_GATEQ]);
+    p.wgs = r.ptr<float>(op.t[S2K_WGRAD_T_WGS]);
+    if (r.absent) return r.fault("wgrad");
     const int32_t* d = op.d;
     p.B = d[S2K_WGRAD_D_B]; p.M = d[S2K_WGRAD_D_M]; p.C = d[S2K_WGRAD_D_C]; p.CTOT = d[S2K_WGRAD_D_CTOT];
     p.H = d[S2K_WGRAD_D_H]; p.W = d[S2K_WGRAD_D_W]; p.KH = d[S2K_WGRAD_D_KH]; p.KW = d[S2K_WGRAD_D_KW];

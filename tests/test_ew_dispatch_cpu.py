@@ -79,7 +79,14 @@ def test_each_variant_report_follows_its_launch():
     assert re.search(r"launch_se_fc_param_grads\(dgate, hs, hpre, pool, dw1, db1, dw2, db2, B, C, Q, c\.stream\);\s*g_s2k_variant = small \? 14 : 0;", src)
     assert len(re.findall(r"g_s2k_variant = ", src)) == len(want) + 1
     api = (CSRC / "s2k_api.hip").read_text()
-    assert len(re.findall(r"g_s2k_variant = 0;", api)) >= 2          # reset before every stage (run and profile)
+    # reset before every stage (run and profile): the shared issue step resets first, and both loops issue through it and nothing else
+    step = re.search(r"static int issue_step\([^)]*\) \{\n(.*?)\n\}\n", api, re.S).group(1)
+    assert step.lstrip().startswith("g_s2k_variant = 0;") and "try_dw_chain(" in step and "check_launch(dispatch(" in step
+    run = api[api.index("int s2k_program_run("):api.index("int s2k_op_launch(")]
+    prof = api[api.rindex("static int profile_impl("):]
+    assert len(re.findall(r"issue_step\(", run)) == 2 and len(re.findall(r"issue_step\(", prof)) == 1          # side / main stream; profile
+    for loop in (run, prof):
+        assert "dispatch(" not in loop and "try_dw_chain(" not in loop
 
 
 def launched():
