@@ -626,8 +626,9 @@ def op_token_gather(m: Mem, o):
     idx = m.view(o["IDX"], (B, Lout), "i32").long()
     fill = m.view(o["FILL"], (C,))
     got = torch.gather(src, 2, idx.clamp(min=0).unsqueeze(1).expand(-1, C, -1))
-    if fill is not None:
-        got = torch.where((idx >= 0).unsqueeze(1), got, fill.view(1, C, 1).expand(B, C, Lout))
+    # idx < 0 takes FILL[c]; without FILL it is 0, as the kernel writes it (plan_random_masking's absent cls slot)
+    fill = fill.view(1, C, 1).expand(B, C, Lout) if fill is not None else torch.zeros_like(got)
+    got = torch.where((idx >= 0).unsqueeze(1), got, fill)
     if o["POS"] >= 0:
         prow = (idx + o["POS_OFF"]) if o["POS_BY_SRC"] else torch.arange(Lout).unsqueeze(0).expand(B, -1)
         nrows = int(prow.max().item()) + 1

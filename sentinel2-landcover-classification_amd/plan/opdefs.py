@@ -194,7 +194,7 @@ OPS: dict[str, tuple[list[str], list[str], list[str], list[str]]] = {
     # DEC_IDX[b][0] = 0 (cls);  DEC_IDX[b][1 + l] = IDS[b][l] < KEEP ? 1 + IDS[b][l] : -1 (mask token)
     "IDS_TO_DEC_IDX": (["IDS", "DEC_IDX"], [], ["B", "L", "KEEP"], []),
     # OUT[b][c][j] = (i = IDX[b][j]) >= 0 ? IN[b][c][i] : FILL[c];  then + POS[(POS_BY_SRC ? i + POS_OFF : j) * C + c]
-    # (POS is token-major, as the reference's pos_embed parameters)
+    # (POS is token-major, as the reference's pos_embed parameters; FILL null: 0 where IDX < 0)
     "TOKEN_GATHER": (["IN", "IDX", "FILL", "POS", "OUT"], [], ["B", "C", "LIN", "LOUT", "POS_BY_SRC", "POS_OFF", "LIN_S", "LOUT_S"], []),
     # DIN[b][c][i] = DOUT[b][c][j] for i = IDX[b][j] >= 0 (other DIN entries zero);  DFILL[c] += sum_{b, j: IDX < 0} DOUT[b][c][j]
     "TOKEN_SCATTER": (["DOUT", "IDX", "DIN", "DFILL"], [], ["B", "C", "LIN", "LOUT", "LIN_S", "LOUT_S"], []),

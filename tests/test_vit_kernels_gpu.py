@@ -466,6 +466,23 @@ def test_token_gather_without_fill_and_pos(LinS, LoutS):
     assert (got[..., Lout:] == 0).all()
 
 
+def test_token_gather_without_fill_takes_zero_for_a_negative_index():
+    """FILL = None with a -1 index: plan_random_masking gathers through ENC_IDX, whose column 0 is the absent cls slot.  The stage
+    writes 0 there (opdefs.py, TOKEN_GATHER); the emulator used to copy token 0 instead (found by tests/test_vit_stages_gpu.py)."""
+    c = Case(38)
+    B, C, Lin, Lout = 2, 12, 16, 9
+    src = c.t("in", (B, C, Lin))
+    idxv = torch.stack([torch.randperm(Lin, generator=c.gen)[:Lout] for _ in range(B)])
+    idxv[:, 0] = -1
+    idxv[1, 5] = -1
+    idx = c.t("idx", (B, Lout), idxv, "i32")
+    out = c.t("out", (B, C, Lout), "nan")
+    bufs = _execute(c, [("TOKEN_GATHER", dict(IN=src, IDX=idx, FILL=None, POS=None, OUT=out, B=B, C=C, LIN=Lin, LOUT=Lout, POS_BY_SRC=0,
+                                              POS_OFF=0, LIN_S=0, LOUT_S=0))])
+    got = _check_exact(c, bufs, "out", "token_gather without fill")
+    assert (got[:, :, 0] == 0).all() and (got[1, :, 5] == 0).all() and (got[0, :, 1:] != 0).all()
+
+
 GATHER_STRIDE = (3, 700, 1100, 1001)        # 2,102,100 output elements on a grid of 8192 x 256
 SCATTER_STRIDE = (5, 3300, 9, 7)            # 16,500 rows on a grid of 4096 x 4 rows
 

@@ -13,6 +13,7 @@ from s2lc_amd.plan import opdefs as D
 from s2lc_amd.plan import vit_plan as V
 from tests.helpers import MAE_CASES, SEG_CASES, mae_inputs, rel_err, seg_inputs
 from tests.plan_harness import emulate, flat_from_state, fview, make_bases_vit, out_view
+from tests.plan_harness import method_bases as _method_bases
 
 
 def _mae_spec(cfg: P.MaeCfg, decoder=True) -> V.MaeSpec:
@@ -120,29 +121,6 @@ def test_seg_programs_match_oracle(tag, wide):
 
 
 # ---- separately callable methods (forward_encoder / forward_decoder / forward_loss / random_masking) ---------------------
-def _method_bases(plan, fp, fb, inputs: dict, noise: dict, wide=True):
-    """Packed X / NOISE / DOUT / DX bases of a MethodPlan for the emulator."""
-    from s2lc_amd.plan import opdefs as D
-    from tests.plan_harness import _bytes
-
-    fd = torch.float64
-    bases = make_bases_vit(type("P", (), dict(ws_bytes=plan.ws_bytes, aux_bytes=plan.aux_bytes, out_bytes=plan.out_bytes, noise_bytes=max(plan.noise_bytes, 4),
-                                               dout_shape=(1,), const_table=plan.const_table, wpack_bytes=plan.wpack_bytes))(),
-                           fp, fb, torch.zeros(1), torch.zeros(1), wide)
-    k = 2
-    mem = __import__("oracle.ops_ref", fromlist=["Mem"])
-    for base, size in (("X", plan.x_bytes), ("DOUT", plan.dout_bytes), ("DX", plan.dx_bytes), ("NOISE", max(plan.noise_bytes, 8))):
-        bases[D.BASE[base]] = torch.zeros(k * ((size + 7) // 8 * 8) + 64, dtype=torch.uint8)
-    m = mem.Mem(bases, wide, (D.BASE["CONST"],))
-    for name, t in inputs.items():
-        r = plan.inputs[name]
-        m.view(r.ref, r.shape, r.dtype).copy_(t)
-    for name, t in noise.items():
-        r = plan.noise[name]
-        m.view(r.ref, r.shape, r.dtype).copy_(t)
-    return bases, m
-
-
 def test_method_plans_match_oracle_float64():
     cfg, sd, x, noise, ratio = mae_inputs("small_bs2")
     B = x.shape[0]
