@@ -330,6 +330,54 @@ int s2k_rasterize(const int* verts, int V, const int* ring_start, const int* rin
                   void* stream);
 size_t s2k_rasterize_workspace(int M, int S);
 
+/* Zonal statistics: per-zone class votes and band statistics, the majority class per zone and painting a per-zone table back into a
+ * raster (zonal.py; csrc/zonal.hip).  Four plain functions like s2k_rasterize, not stage kinds: the stage table stays at 55 kinds and
+ * S2K_ABI_VERSION at 2.  Each is ONE plain launch on `stream`: no grid-wide barrier, no host read.
+ *
+ * Definitions (they are the oracle; the reference asks these questions per dataset and per tile on the host, never per object).
+ *   zone         [M][H][W], int32 (zone_bytes == 4) or int64 (== 8): the RAW zone value of every pixel.
+ *   zone_stride  0: raw values are global ids, as rasterize(burn = index) writes them; zone_limit = Z.
+ *                > 0: raw values are ids inside their own map, as s2k_classmap_components writes them with zone_stride = H * W;
+ *                zone_limit = zone_stride, and M * zone_stride == Z is required.
+ *   KEY          of pixel (m, y, x) with raw value r: r < 0 (the fill = -1 convention): the pixel has NO KEY and is skipped silently;
+ *                r >= zone_limit, compared in 64 bits (an int64 value is never truncated): no key either, and 1 is OR-ed into status[0];
+ *                otherwise z = r + m * zone_stride, which lies in [0, Z).  Tables have Z rows; 1 <= Z < 2^31.
+ *   status       u32 [1], OR-ed into, never cleared: 1 = a raw zone value at or above zone_limit was met (and skipped).
+ * s2k_zonal_histogram.  cls: [M][H][W], uint8 (cls_bytes == 1) or int64 (== 8); src_lut: int32[256] or NULL, only with a 1-byte cls: the
+ *   class of a pixel is then src_lut[raw].  1 <= K <= 32.  hist: i64 [Z][K], ADDED to: for every pixel with a key z and a class c in
+ *   [0, K): hist[z][c] += 1.  A class outside [0, K) is skipped silently.
+ * s2k_zonal_bands.  vals: int16 [M][C][H][W], 1 <= C <= 16.  A band value v of a pixel with key z is COUNTED for band c unless has_nodata
+ *   is 1 and v == nodata (for that band only; the other bands of the pixel are judged on their own).  Outputs, all [Z][C]: for every
+ *   counted value   count[z][c] += 1;  sum[z][c] += v;  sumsq[z][c] += v * v   (i64, ADDED to);
+ *                   min[z][c] = min(min[z][c], v);  max[z][c] = max(max[z][c], v)   (i32; the caller initialises them, usually to
+ *   INT32_MAX and INT32_MIN, and a (z, c) without a counted value keeps what it held).  sum is exact; sumsq is exact while it stays
+ *   below 2^63, which 2^33 values of magnitude 32768 cannot reach.
+ * s2k_zonal_majority.  hist: i64 [Z][K]; votes: bit mask of the classes that vote (non-zero, no bit at K or above); min_count >= 1.
+ *   best[z] = the largest hist[z][c] over the voting classes c (signed comparison);
+ *   out_cls[z] (i32 [Z]) = the LOWEST voting class c with hist[z][c] == best[z] if best[z] >= min_count, else `fill` (any int32);
+ *   out_best (i64 [Z] or NULL)[z] = best[z].  No zone raster and no status.
+ * s2k_zonal_paint.  table: i32 [Z]; dst: [M][H][W], dst_bytes 1 (uint8), 4 (int32) or 8 (int64).  A pixel with a key z and
+ *   table[z] >= 0 gets table[z], stored by conversion (a 1-byte dst takes its low byte).  Every other pixel - no key, or a negative
+ *   table entry - gets `fill` in mode 0 and keeps what dst held in mode 1.
+ * Every argument is validated on the host before anything is launched: S2K_EFAULT, reported first, for a NULL zone, cls, hist, vals,
+ * count, sum, sumsq, min, max, table, dst, out_cls or (where the entry takes one) status; S2K_EINVAL for zone_bytes other than 4 or 8,
+ * cls_bytes other than 1 or 8, dst_bytes other than 1, 4 or 8, src_lut with an 8-byte cls, K outside 1..32, C outside 1..16, has_nodata
+ * other than 0 or 1, Z, M, H or W below 1, zone_stride < 0, zone_stride > 0 with M * zone_stride != Z, H * W >= 2^31 (offsets inside a map
+ * are 32-bit; the map offset is 64-bit), M * ceil(H / 16) * ceil(W / 256) >= 2^31 (histogram and bands: one workgroup per 16 x 256 block
+ * of a map) or ceil(M * H * W / 256) >= 2^31 (paint: one thread per pixel), votes zero or with a bit at K or above, min_count < 1, mode
+ * other than 0 or 1, fill outside 0..255 with a 1-byte dst.  Messages begin with "zonal: ".
+ * All results are integer functions of the inputs: bit-identical from run to run, whatever the order in which workgroups arrive, and
+ * independent of how M is split over several calls (zone_stride == 0).  Quad loads are used when W % 4 == 0 and the rasters are 16-byte
+ * aligned; otherwise every element is read on its own.  No allocation, no copy, no synchronisation, no host read. */
+int s2k_zonal_histogram(const void* zone, int zone_bytes, int zone_stride, const void* cls, int cls_bytes, const int* src_lut, int M, int H,
+                        int W, int Z, int K, long long* hist, unsigned* status, void* stream);
+int s2k_zonal_bands(const void* zone, int zone_bytes, int zone_stride, const short* vals, int M, int C, int H, int W, int Z, int nodata,
+                    int has_nodata, long long* count, long long* sum, long long* sumsq, int* min, int* max, unsigned* status, void* stream);
+int s2k_zonal_majority(const long long* hist, int Z, int K, unsigned votes, long long min_count, int fill, int* out_cls, long long* out_best,
+                       void* stream);
+int s2k_zonal_paint(const void* zone, int zone_bytes, int zone_stride, const int* table, int M, int H, int W, int Z, void* dst, int dst_bytes,
+                    int mode, int fill, unsigned* status, void* stream);
+
 /* Measured ceilings of the current device for roofline reporting (bench.py): sustained v_mfma_f32_32x32x2_f32 rate with every
  * SIMD issuing back to back (TFLOP/s), the shader clock held meanwhile (MHz), and a float4 stream copy (GB/s, read + write).
  * `scratch`: >= 64 MiB of device memory (size the copy past the caches: 1 GiB+).  Synchronises `stream`.  Not on the hot path. */

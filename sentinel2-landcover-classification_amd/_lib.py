@@ -74,6 +74,15 @@ def lib() -> ctypes.CDLL:
     L.s2k_rasterize.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.s2k_rasterize_workspace.restype = ctypes.c_size_t
     L.s2k_rasterize_workspace.argtypes = [i32] * 2
+    i64 = ctypes.c_longlong
+    L.s2k_zonal_histogram.restype = i32
+    L.s2k_zonal_histogram.argtypes = [vp, i32, i32, vp, i32, vp] + [i32] * 5 + [vp, vp, vp]
+    L.s2k_zonal_bands.restype = i32
+    L.s2k_zonal_bands.argtypes = [vp, i32, i32, vp] + [i32] * 7 + [vp] * 7
+    L.s2k_zonal_majority.restype = i32
+    L.s2k_zonal_majority.argtypes = [vp, i32, i32, u32, i64, i32, vp, vp, vp]
+    L.s2k_zonal_paint.restype = i32
+    L.s2k_zonal_paint.argtypes = [vp, i32, i32, vp] + [i32] * 4 + [vp, i32, i32, i32, vp, vp]
     if L.s2k_abi_version() != 2:
         raise S2kError(f"libs2k ABI {L.s2k_abi_version()} != 2")
     if L.s2k_op_size() != D.OP_BYTES or OP_DTYPE.itemsize != D.OP_BYTES:
@@ -271,6 +280,49 @@ def rasterize(verts, ring_start, ring_shape, values, origins, dst, dims, mode: i
 def rasterize_workspace(M: int, S: int) -> int:
     """bytes of the `work` buffer of s2k_rasterize for M tiles and S shapes"""
     return int(lib().s2k_rasterize_workspace(int(M), int(S)))
+
+
+ZONAL_PAINT_MODES = {"fill": 0, "keep": 1}          # what s2k_zonal_paint does with a pixel it has no value for (include/s2k.h)
+
+
+def zonal_histogram(zone, zone_stride: int, cls, src_lut, dims, hist, status, stream: int, zone_bytes: int | None = None,
+                    cls_bytes: int | None = None) -> int:
+    """s2k_zonal_histogram (include/s2k.h) as it is: tensors (or None) for the five pointers, dims = (M, H, W, Z, K); the element widths
+    default to the tensors' own.  Returns the library's code; the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    zb = (4 if zone is None else zone.element_size()) if zone_bytes is None else int(zone_bytes)
+    cb = (8 if cls is None else cls.element_size()) if cls_bytes is None else int(cls_bytes)
+    return lib().s2k_zonal_histogram(ptr(zone), zb, int(zone_stride), ptr(cls), cb, ptr(src_lut), *[int(d) for d in dims], ptr(hist), ptr(status),
+                                     stream)
+
+
+def zonal_bands(zone, zone_stride: int, vals, dims, nodata, count, total, sumsq, lo, hi, status, stream: int,
+                zone_bytes: int | None = None) -> int:
+    """s2k_zonal_bands (include/s2k.h) as it is: tensors (or None) for the eight pointers, dims = (M, C, H, W, Z), `nodata` an int or None
+    (no value is skipped).  Returns the library's code; the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    zb = (4 if zone is None else zone.element_size()) if zone_bytes is None else int(zone_bytes)
+    return lib().s2k_zonal_bands(ptr(zone), zb, int(zone_stride), ptr(vals), *[int(d) for d in dims], 0 if nodata is None else int(nodata),
+                                 0 if nodata is None else 1, ptr(count), ptr(total), ptr(sumsq), ptr(lo), ptr(hi), ptr(status), stream)
+
+
+def zonal_majority(hist, dims, votes: int, min_count: int, fill: int, out_cls, out_best, stream: int) -> int:
+    """s2k_zonal_majority (include/s2k.h) as it is: tensors (or None) for the three pointers, dims = (Z, K).  Returns the library's code;
+    the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    Z, K = (int(d) for d in dims)
+    return lib().s2k_zonal_majority(ptr(hist), Z, K, int(votes) & 0xffffffff, int(min_count), int(fill), ptr(out_cls), ptr(out_best), stream)
+
+
+def zonal_paint(zone, zone_stride: int, table, dims, dst, mode: int, fill: int, status, stream: int, zone_bytes: int | None = None,
+                dst_bytes: int | None = None) -> int:
+    """s2k_zonal_paint (include/s2k.h) as it is: tensors (or None) for the four pointers, dims = (M, H, W, Z); the element widths default
+    to the tensors' own.  Returns the library's code; the library validates every argument on the host before it launches."""
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    zb = (4 if zone is None else zone.element_size()) if zone_bytes is None else int(zone_bytes)
+    db = (8 if dst is None else dst.element_size()) if dst_bytes is None else int(dst_bytes)
+    return lib().s2k_zonal_paint(ptr(zone), zb, int(zone_stride), ptr(table), *[int(d) for d in dims], ptr(dst), db, int(mode), int(fill),
+                                 ptr(status), stream)
 
 
 MAE_PANELS = {"original": 0, "masked": 1, "pasted": 2, "reconstruction": 3}      # panel codes of s2k_mae_panels (include/s2k.h)

@@ -70,4 +70,21 @@ int launch_rasterize(const int* verts, int V, const int* ring_start, const int* 
                      hipStream_t st);
 size_t rasterize_workspace(int M, int S);
 
+// zonal.hip
+int check_zonal_histogram(const void* zone, int zone_bytes, int zone_stride, const void* cls, int cls_bytes, const int* src_lut, int M, int H,
+                          int W, int Z, int K, long long* hist, unsigned* status);
+int launch_zonal_histogram(const void* zone, int zone_bytes, int zone_stride, const void* cls, int cls_bytes, const int* src_lut, int M, int H,
+                           int W, int Z, int K, long long* hist, unsigned* status, hipStream_t st);
+int check_zonal_bands(const void* zone, int zone_bytes, int zone_stride, const short* vals, int M, int C, int H, int W, int Z, int nodata,
+                      int has_nodata, long long* count, long long* sum, long long* sumsq, int* mn, int* mx, unsigned* status);
+int launch_zonal_bands(const void* zone, int zone_bytes, int zone_stride, const short* vals, int M, int C, int H, int W, int Z, int nodata,
+                       int has_nodata, long long* count, long long* sum, long long* sumsq, int* mn, int* mx, unsigned* status, hipStream_t st);
+int check_zonal_majority(const long long* hist, int Z, int K, unsigned votes, long long min_count, int fill, int* out_cls, long long* out_best);
+int launch_zonal_majority(const long long* hist, int Z, int K, unsigned votes, long long min_count, int fill, int* out_cls, long long* out_best,
+                          hipStream_t st);
+int check_zonal_paint(const void* zone, int zone_bytes, int zone_stride, const int* table, int M, int H, int W, int Z, void* dst, int dst_bytes,
+                      int mode, int fill, unsigned* status);
+int launch_zonal_paint(const void* zone, int zone_bytes, int zone_stride, const int* table, int M, int H, int W, int Z, void* dst, int dst_bytes,
+                       int mode, int fill, unsigned* status, hipStream_t st);
+
 }  // namespace s2k

@@ -518,6 +518,30 @@ int s2k_rasterize(const int* verts, int V, const int* ring_start, const int* rin
 
 size_t s2k_rasterize_workspace(int M, int S) { return rasterize_workspace(M, S); }
 
+int s2k_zonal_histogram(const void* zone, int zone_bytes, int zone_stride, const void* cls, int cls_bytes, const int* src_lut, int M, int H,
+                        int W, int Z, int K, long long* hist, unsigned* status, void* stream) {
+    return guarded_call("zonal: histogram", stream, check_zonal_histogram, launch_zonal_histogram, zone, zone_bytes, zone_stride, cls, cls_bytes,
+                        src_lut, M, H, W, Z, K, hist, status);
+}
+
+int s2k_zonal_bands(const void* zone, int zone_bytes, int zone_stride, const short* vals, int M, int C, int H, int W, int Z, int nodata,
+                    int has_nodata, long long* count, long long* sum, long long* sumsq, int* min, int* max, unsigned* status, void* stream) {
+    return guarded_call("zonal: bands", stream, check_zonal_bands, launch_zonal_bands, zone, zone_bytes, zone_stride, vals, M, C, H, W, Z, nodata,
+                        has_nodata, count, sum, sumsq, min, max, status);
+}
+
+int s2k_zonal_majority(const long long* hist, int Z, int K, unsigned votes, long long min_count, int fill, int* out_cls, long long* out_best,
+                       void* stream) {
+    return guarded_call("zonal: majority", stream, check_zonal_majority, launch_zonal_majority, hist, Z, K, votes, min_count, fill, out_cls,
+                        out_best);
+}
+
+int s2k_zonal_paint(const void* zone, int zone_bytes, int zone_stride, const int* table, int M, int H, int W, int Z, void* dst, int dst_bytes,
+                    int mode, int fill, unsigned* status, void* stream) {
+    return guarded_call("zonal: paint", stream, check_zonal_paint, launch_zonal_paint, zone, zone_bytes, zone_stride, table, M, H, W, Z, dst,
+                        dst_bytes, mode, fill, status);
+}
+
 int s2k_selftest_mfma(const float* a, const float* b, float* d, void* stream) {
     return guarded_call("selftest", stream, check_mfma_selftest, launch_mfma_selftest, a, b, d);
 }

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from .. import classmap as CM
+from .. import zonal as ZN
 from ..plan import opdefs as D
 from . import dataset_stats as DS
 from . import quicklook as QL
@@ -368,6 +369,57 @@ class GpuTilePipeline:
             CM.launch_components(src, K, conn, 0, work[0], work[1], status, counts[m0:m0 + step], src_lut=self.lut)
         CM.raise_status(status)
         return counts
+
+    def _zone_rasters(self, zones, indices, need_labels: bool):
+        """(idx, zones) for the zonal methods: `zones` int32 / int64 [M, H, W], one raster per selected tile, of the tiles' size"""
+        if self.raw is None:
+            raise RuntimeError("call load() first")
+        z = ZN._check_zones(zones)
+        N, _, H, W = self.raw.shape
+        M = N if indices is None else torch.as_tensor(indices).numel()
+        if zones.dim() != 3 or tuple(z.shape) != (M, H, W):
+            raise ValueError(f"zones must be [M, H, W] = [{M}, {H}, {W}]: one raster per selected tile")
+        return self._stats_index(indices, need_labels), z
+
+    @torch.no_grad()
+    def zonal_label_histogram(self, zones, num_zones: int, indices=None, num_classes: int | None = None) -> torch.Tensor:
+        """int64 [num_zones, num_classes] on the device (num_classes=None: the label map's own class count, at most 32): how many pixels of every label class (after the label map's remap) lie in
+        every zone of `zones` (int32 or int64 [M, H, W], one raster per selected tile, global zone ids, negative = no zone:
+        `classmap.rasterize(..., burn="index", fill=-1)`) - `zonal.histogram` of the resident labels read through the pipeline's label
+        table inside the kernel.  Remapped labels outside [0, num_classes) are not counted."""
+        K = CM.check_classes(self.label_classes if num_classes is None else num_classes)
+        Z, _ = ZN._check_num_zones(num_zones, 1, False)
+        idx, z = self._zone_rasters(zones, indices, need_labels=True)
+        ZN._need_gpu(z)
+        hist = torch.zeros(Z, K, dtype=torch.int64, device=self.device)
+        status = CM.new_status(self.device)
+        H, W = z.shape[1:]
+        step = CM.maps_per_chunk(H, W, 1)                       # the gathered label rasters of a chunk
+        for m0 in range(0, idx.numel(), step):
+            src = self.labels.index_select(0, idx[m0:m0 + step].to(self.device))
+            ZN.launch_histogram(z[m0:m0 + step], 0, src, Z, K, hist, status, src_lut=self.lut)
+        ZN.raise_status(status)
+        return hist
+
+    @torch.no_grad()
+    def zonal_band_stats(self, zones, num_zones: int, indices=None, nodata=None):
+        """`zonal.ZonalStats` [num_zones, C] of the resident raw tiles inside every zone of `zones` (as for `zonal_label_histogram`):
+        count, sum, sum of squares, minimum and maximum per zone and band, exact; nodata=v leaves a band value equal to v out."""
+        Z, _ = ZN._check_num_zones(num_zones, 1, False)
+        nd = None if nodata is None else ZN._check_int(nodata, ZN.INT32_MIN, ZN.INT32_MAX, "nodata")
+        idx, z = self._zone_rasters(zones, indices, need_labels=False)
+        C, H, W = self.raw.shape[1:]
+        if C > ZN.MAX_BANDS:
+            raise ValueError(f"zonal band statistics take at most {ZN.MAX_BANDS} bands")
+        ZN._need_gpu(z)
+        stats = ZN.new_stats((Z, C), self.device)
+        status = CM.new_status(self.device)
+        step = CM.maps_per_chunk(H, W, 2 * C)                   # the gathered tiles of a chunk
+        for m0 in range(0, idx.numel(), step):
+            vals = self.raw.index_select(0, idx[m0:m0 + step].to(self.device))
+            ZN.launch_bands(z[m0:m0 + step], 0, vals, Z, nd, stats, status)
+        ZN.raise_status(status)
+        return stats
 
     def weighted_indices(self, weights, num_samples: int, generator: torch.Generator | None = None) -> torch.Tensor:
         """int64 [num_samples] positions drawn with replacement in proportion to `weights`, on the host: exactly what

@@ -24,6 +24,7 @@ import math
 import torch
 
 from . import classmap as CM
+from . import zonal as ZN
 from .data import quicklook as QL
 from .render import overlay
 from .stage_call import StageCall
@@ -185,6 +186,40 @@ class TilePredictor:
         maximum of the same stored values."""
         CM.check_measure(measure)
         return CM.confidence(self.predict_blend(indices), "probs" if self.mode == 1 else "logits", measure, 1.0, min_confidence, reject_to)
+
+    @torch.no_grad()
+    def predict_zones(self, zones, num_zones: int, indices=None, votes=None, min_count: int = 1, paint: bool = False,
+                      majority: int | None = None, iterations: int = 1, min_area: int | None = None, connectivity: int = 4):
+        """Object-based classification of the selected tiles: (zone_class int32 [num_zones], hist int64 [num_zones, num_classes]) on
+        the device - `zonal.histogram` of `predict(indices, majority, iterations, min_area, connectivity)` inside every zone of `zones`
+        (int32 or int64 [M, H, W], one raster per selected tile, global ids, negative = no zone) and its `zonal.majority(hist, votes,
+        min_count)`: the lowest class with the most predicted pixels, -1 for a zone with fewer than `min_count` of them.  paint=True
+        adds int64 [M, H, W]: the predicted maps with every classified zone painted in its class, all other pixels as predicted."""
+        Z, _ = ZN._check_num_zones(num_zones, 1, False)
+        vb = CM.class_bits(votes, self.K, "votes")
+        if vb == 0:
+            raise ValueError("votes must name at least one class")
+        n = ZN._check_count(min_count)
+        self._post(majority, iterations, min_area, connectivity)
+        pipe = self.pipe
+        if pipe.raw is None:
+            raise RuntimeError("call load() first")
+        z = ZN._check_zones(zones)
+        M = pipe.raw.shape[0] if indices is None else torch.as_tensor(indices).numel()
+        if zones.dim() != 3 or tuple(z.shape) != (M,) + tuple(pipe.raw.shape[2:]):
+            raise ValueError("zones must be [M, H, W]: one raster of the tiles' size per selected tile")
+        idx = pipe._stats_index(indices, need_labels=False)              # ValueError first, then the refusal to run off the GPU
+        ZN._need_gpu(z)
+        mask = self.predict(idx, majority, iterations, min_area, connectivity)
+        hist = torch.zeros(Z, self.K, dtype=torch.int64, device=mask.device)
+        cls = torch.empty(Z, dtype=torch.int32, device=mask.device)
+        status = CM.new_status(mask.device)
+        ZN.launch_histogram(z, 0, mask, Z, self.K, hist, status)
+        ZN.launch_majority(hist, Z, self.K, vb, n, -1, cls)
+        if paint:
+            ZN.launch_paint(z, 0, cls, Z, mask, ZN.KEEP, 0, status)
+        ZN.raise_status(status)
+        return (cls, hist, mask) if paint else (cls, hist)
 
     @torch.no_grad()
     def evaluate_calibration(self, cal, indices=None) -> None:
